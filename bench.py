@@ -32,8 +32,17 @@ reference's own multi-threaded CPU grid (cpu_baseline, N = 1).
 
 --log-n L instead fixes 2^L points per rank (weak scaling, the round-3 mode).
 
+A plain run does only what the headline needs: inputs, the CHES table, the
+warm-up batch, the K timed steps, then the line with `value`, `ms_per_step`,
+the timed batch's own accumulation time and the HBM roofline priced with it.
+Everything "reported beside it" above, the parity checks, the VALU probe, the
+profiled single MSM (the phase split, `kernel_ms_alone`) and the CPU baseline run
+only with --full, where the --no-* switches still drop single parts.
+--dump-outputs DIR writes the last timed step's result (dump_outputs); the
+inputs are fixed points and seeded scalars, identical from run to run.
+
 Usage:
-  python bench.py [--gpus N --steps K --warmup W]                 (N = 1)
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N = 1)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -181,6 +190,19 @@ def make_scalar_sets(m, n, K, rank, world):
     return host
 
 
+def dump_outputs(m, out_dir, G, jac):
+    """--dump-outputs: the MSM the last timed step returned, as float32 arrays of
+    byte values (exact).  The engine hands its caller a Jacobian point whose
+    representative depends on the order of the bucket additions, so two builds
+    are compared on the point itself: its affine coordinates in blst's layout
+    (x | y, 96 G bytes) and its compressed form (48 G bytes), the key every
+    parity check of this file uses."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, raw in (("msm_last_affine", m.to_affine(G, jac)), ("msm_last_compressed", m.compress(G, jac))):
+        np.save(os.path.join(out_dir, name + ".npy"), np.frombuffer(raw, dtype=np.uint8).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -219,7 +241,18 @@ def main():
     ap.add_argument("--multi-context", type=int, default=0, metavar="D",
                     help="N = 1: also time configs[3] (2^21 points) through ONE process driving D shards "
                          "(msm_ches_ctx_create_multi; devices 0..D-1, or D shards on device 0 with --one-device)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the line can report: the resident / sync / "
+                         "other-method / other-config / shard legs, the golden parity checks, the VALU probe and the "
+                         "profiled single MSM behind the roofline block, the CPU baseline (each still has its --no-* "
+                         "switch).  Without it the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned, as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        if args.multi_context:
+            ap.error("--multi-context is a --full leg")
+        args.no_compare = args.no_cpu_baseline = args.no_configs = args.no_shards = args.no_weak_leg = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -259,8 +292,9 @@ def main():
     log(f"[rank {rank}] inputs generated in {time.time() - t0:.1f}s (points {start}..{start + n}, {K} scalar sets)")
     stream = torch.cuda.current_stream(dev)
     sp = stream.cuda_stream
-    d_all = host.to(dev)  # the same K sets resident in HBM (resident / sync legs)
-    hptr, dptr, SS = host.data_ptr(), d_all.data_ptr(), n * 32
+    # the same K sets resident in HBM: the resident / sync legs of --full (and the --setup-batch study knob)
+    d_all = host.to(dev) if args.full or args.setup_batch else None
+    hptr, dptr, SS = host.data_ptr(), None if d_all is None else d_all.data_ptr(), n * 32
     add = mdist.engine_add(G)
 
     def keys(jacs):  # canonical comparison key: the compressed affine point (Jacobians differ in representative)
@@ -350,7 +384,8 @@ def main():
             legs["ches_sync"] = leg(n * world * K / sel, sel / K * 1e3, batch_eq_sync)
         else:
             batch_eq_sync = None
-        mult(0)  # one profiled synchronous MSM for the phase split
+        if args.full:
+            mult(0)  # one profiled synchronous MSM for the phase split
         phases = ctx.phase_times()
     else:
         for k in range(W):
@@ -361,13 +396,17 @@ def main():
         batch_eq_sync = None
         legs[args.method + "_sync_h2d"] = leg(n * world * K / elapsed, elapsed / K * 1e3)
 
-    # ---- parity ----
-    gold = json.load(open(os.path.join(REPO, "tests", "golden", f"msm_g{G}.json")))
-    want = [c["compressed"] for c in gold["cases"]
-            if c["n"] == n * world and c["seed"] == 1 and c["case"] == "rand"]
-    golden_ok = (m.compress(G, res[0]).hex() == want[0]) if want else None
-    cross = None
-    if world > 1 and not want:  # no golden for this total size: plain Pippenger on the same shard and set 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(m, args.dump_outputs, G, res[-1])
+
+    # ---- parity (--full) ----
+    want, golden_ok, cross = [], None, None
+    if args.full:
+        gold = json.load(open(os.path.join(REPO, "tests", "golden", f"msm_g{G}.json")))
+        want = [c["compressed"] for c in gold["cases"]
+                if c["n"] == n * world and c["seed"] == 1 and c["case"] == "rand"]
+        golden_ok = (m.compress(G, res[0]).hex() == want[0]) if want else None
+    if args.full and world > 1 and not want:  # no golden for this total size: plain Pippenger on the same shard and set 0
         pctx = m.MSMContext(G, local, args.window)
         pctx.set_points(pts, n, stream=sp)
         pp = pctx.mult(dptr, 255, stride=32, on_device=True, stream=sp)
@@ -378,7 +417,7 @@ def main():
     # the device's VALU ceilings, measured now (after the timed region, GPU warm):
     # twice, keeping the higher rate (the first call also warms the probe kernels)
     probe = None
-    for _ in range(2):
+    for _ in range(2 if args.full else 0):
         p = valu_probe(m, local)
         if p is not None:
             probe = p if probe is None else {k: max(probe[k], p[k]) for k in p}
@@ -455,7 +494,8 @@ def main():
         except Exception:
             traffic = None
     mads, mads_src = isa_mads_per_madd(G)
-    acc_alone = phases.get("accumulate") and phases["accumulate"] / 1e3
+    # the accumulation of the profiled single MSM (--full); a plain run has only the timed batch's figure
+    acc_alone = (phases.get("accumulate") and phases["accumulate"] / 1e3) if args.full or not batched else None
     # VALU roofline, priced against ceilings measured in THIS run on this device
     # (msm_valu_probe, csrc/probe.hip): the register-resident G1 madd loop (the
     # accumulation's body without its row loads) and the chip's v_mad_u64_u32
@@ -473,6 +513,8 @@ def main():
             "mad_frac": mad_frac, "mad_frac_alone": mad_frac_alone, "mads_per_madd": mads,
             "mad_peak_T": round(pk["mad"] / 1e12, 3), "fpmul_peak_G": round(pk["fpmul"] / 1e9, 2),
             "peak_basis": "this run (msm_valu_probe)" if probe else "round-2 constants (probe unavailable)"}
+    if not args.full:  # the VALU block is priced by the probe's own launches
+        valu = {}
 
     parity = golden_ok if golden_ok is not None else cross
     if batch_eq_sync is False:
@@ -489,6 +531,7 @@ def main():
         "steps": K,
         "warmup": W,
         "ms_per_step": round(elapsed / K * 1e3, 4),
+        "full": args.full,
         "higher_is_better": True,
         "scaling": scaling,
         "vs_baseline": None,

@@ -50,6 +50,29 @@ def test_ches_config_per_group_and_shard_size():
     assert bench.ches_config(20, 1, 1) == (20, 1)
 
 
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: one float32 .npy per name holding the byte values of the
+    last step's point (affine and compressed), exact and reproducible."""
+    import numpy as np
+
+    class Engine:  # the two host conversions dump_outputs calls
+        @staticmethod
+        def to_affine(group, jac):
+            return bytes(jac[:96 * group])
+
+        @staticmethod
+        def compress(group, jac):
+            return bytes(jac[:48 * group])
+
+    jac = bytes(range(144))
+    out = tmp_path / "dump"
+    bench.dump_outputs(Engine, str(out), 1, jac)
+    assert sorted(p.name for p in out.iterdir()) == ["msm_last_affine.npy", "msm_last_compressed.npy"]
+    aff, com = np.load(out / "msm_last_affine.npy"), np.load(out / "msm_last_compressed.npy")
+    assert aff.dtype == com.dtype == np.float32 and aff.shape == (96,) and com.shape == (48,)
+    assert aff.astype(np.uint8).tobytes() == jac[:96] and com.astype(np.uint8).tobytes() == jac[:48]
+
+
 def test_default_warmup_is_one_batch():
     """bench.py's default warm-up is one untimed batch as long as the timed one
     (the first short-warm-up batch runs below steady-state clocks,

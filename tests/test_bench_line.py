@@ -1,4 +1,4 @@
-"""The bench line's shape, on the line bench.py printed in the final-tree
+"""The bench line's shape, on the line bench.py --full printed in the final-tree
 session (profiles/r06_bench.json, N = 1) and a gloo rehearsal (N = 2 / 8,
 profiles/r06_strong_rehearsal.txt): the contract keys, the roofline and
 cpu_baseline objects, every leg compact, and the whole line small enough for
@@ -55,7 +55,7 @@ def test_rehearsal_lines_are_strong_scaling_with_parity():
 
 
 def test_g2_line_shape():
-    """configs[4]'s line (bench.py --group 2): its own metric name, the G2
+    """configs[4]'s line (bench.py --full --group 2): its own metric name, the G2
     roofline priced on the probe's mad rate, parity, under 7 KB."""
     raw = _last_line(os.path.join(REPO, "profiles", "r06_bench_g2.json"))
     assert len(raw) < 7000

@@ -15,7 +15,7 @@ for step in "$@"; do
     new) timeout -k 10 500 python -u -m pytest tests/test_gpu_batch_one_lane.py -x -v --timeout 300 --timeout-method thread > $O/pytest_new.txt 2>&1; rc=$?; tail -3 $O/pytest_new.txt ;;
     suite) timeout -k 10 700 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest_gpu.txt 2>&1; rc=$?; tail -2 $O/pytest_gpu.txt ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; rc=$?; tail -2 $O/smoke.txt ;;
-    bench) timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err; rc=$?
+    bench) timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?
            python3 tools/bench_summary.py $O/bench.json ;;
     shards) timeout -k 10 400 python -u tools/shard_study.py > $O/shards.txt 2> $O/shards.err; rc=$?; cat $O/shards.txt ;;
     pip) timeout -k 10 500 python -u tools/pip_study.py --windows 13,14 --envs "MSM_FRONT_PHASE=0;MSM_FRONT_PHASE=1;MSM_FRONT_PHASE=1 MSM_PIP_FRONT_GROUP=8;MSM_FRONT_PHASE=1 MSM_PIP_FRONT_GROUP=2" > $O/pip.txt 2> $O/pip.err; rc=$?; cat $O/pip.txt ;;
@@ -31,7 +31,7 @@ for step in "$@"; do
     batchtests) timeout -k 10 500 python -u -m pytest tests/test_gpu_ches.py tests/test_gpu_batch_one_lane.py tests/test_gpu_multi.py -x -v --timeout 300 --timeout-method thread > $O/pytest_batch.txt 2>&1; rc=$?; tail -3 $O/pytest_batch.txt ;;
     tile) timeout -k 10 300 python -u tools/tile_timing.py > $O/tile.txt 2> $O/tile.err; rc=$?; cat $O/tile.txt; grep "\[tile\]" $O/tile.err ;;
     rehearse) for N in 2 4 8; do
-        timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29560 + N)) bench.py --gpus $N --dist-backend gloo --one-device --steps 10 --warmup 2 --no-cpu-baseline > $O/n$N.json 2> $O/n$N.err || { rc=1; break; }
+        timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29560 + N)) bench.py --full --gpus $N --dist-backend gloo --one-device --steps 10 --warmup 2 --no-cpu-baseline > $O/n$N.json 2> $O/n$N.err || { rc=1; break; }
         python3 -c "import json; d=json.loads(open('$O/n$N.json').read().strip().splitlines()[-1]); print('N=$N', d['value'], d['scaling'], d['config']['n_total'], d['parity_vs_reference'], {k: (v.get('value'), v.get('parity_vs_reference')) for k, v in d['methods'].items()})"
         rc=0
       done ;;
@@ -41,12 +41,12 @@ for step in "$@"; do
         echo "FG=$fg $(python3 tools/bench_summary.py $O/head_fg$fg.json | head -4 | tr '\n' ' ')"; rc=0
       done ;;
     g2ab) for fg in 1 2; do
-        MSM_FRONT_GROUP=$fg timeout -k 10 300 python -u bench.py --group 2 --no-configs --no-cpu-baseline > $O/g2_fg$fg.json 2> $O/g2_fg$fg.err || { rc=1; break; }
+        MSM_FRONT_GROUP=$fg timeout -k 10 300 python -u bench.py --full --group 2 --no-configs --no-cpu-baseline > $O/g2_fg$fg.json 2> $O/g2_fg$fg.err || { rc=1; break; }
         echo "G2 FG=$fg $(python3 tools/bench_summary.py $O/g2_fg$fg.json | head -3 | tr '\n' ' ')"; rc=0
       done ;;
-    g2) timeout -k 10 400 python -u bench.py --group 2 --no-configs --no-cpu-baseline > $O/bench_g2.json 2> $O/bench_g2.err; rc=$?
+    g2) timeout -k 10 400 python -u bench.py --full --group 2 --no-configs --no-cpu-baseline > $O/bench_g2.json 2> $O/bench_g2.err; rc=$?
         python3 tools/bench_summary.py $O/bench_g2.json ;;
-    prof) cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --no-configs --no-cpu-baseline > $O/prof.json 2> $O/prof.log; rc=$?; cd $R ;;
+    prof) cd "$(mktemp -d)" && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --no-configs --no-cpu-baseline > $O/prof.json 2> $O/prof.log; rc=$?; cd $R ;;
     *) echo "unknown step $step"; rc=2 ;;
   esac
   echo "[$step] rc=$rc $(date +%T)"

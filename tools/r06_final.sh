@@ -16,10 +16,10 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeou
 echo "pytest ok $(date +%T) $(tail -1 $O/pytest_gpu.txt)" &&
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 &&
 echo "smoke ok $(date +%T)" &&
-timeout -k 10 600 python3 -u bench.py > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err &&
 echo "bench ok $(date +%T)" && python3 tools/bench_summary.py $O/bench.json &&
 cd /tmp &&
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --no-configs --no-cpu-baseline --no-shards > $O/prof.json 2> $O/prof.log &&
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --no-configs --no-cpu-baseline --no-shards > $O/prof.json 2> $O/prof.log &&
 echo "rocprof ok $(date +%T)" &&
 python3 $R/tools/roofline_check.py $O/prof.json $O/prof/run_kernel_trace.csv $O/roofline_check.json &&
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 $R/bench.py --steps 2 --warmup 0 --no-cpu-baseline --no-compare --no-batch > $O/pmc_fetch.log 2>&1 &&
@@ -29,12 +29,12 @@ echo "pmc ok $(date +%T)" && grep accumulate_bytes_per_launch $O/pmc_traffic.jso
 timeout -s KILL 120 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $O/pmc_valu -o run -- python3 $R/bench.py --steps 2 --warmup 0 --no-cpu-baseline --no-compare --no-batch > $O/pmc_valu.log 2>&1 &&
 echo "pmc valu ok $(date +%T)" &&
 cd $R &&
-timeout -k 10 400 python3 -u bench.py --group 2 --no-configs --no-cpu-baseline --no-shards > $O/bench_g2.json 2> $O/bench_g2.err &&
+timeout -k 10 400 python3 -u bench.py --full --group 2 --no-configs --no-cpu-baseline --no-shards > $O/bench_g2.json 2> $O/bench_g2.err &&
 python3 tools/bench_summary.py $O/bench_g2.json &&
-timeout -k 10 400 python3 -u bench.py --multi-context 8 --one-device --steps 10 --warmup 2 --no-cpu-baseline --no-configs --no-compare --no-shards > $O/mc8.json 2> $O/mc8.err &&
+timeout -k 10 400 python3 -u bench.py --full --multi-context 8 --one-device --steps 10 --warmup 2 --no-cpu-baseline --no-configs --no-compare --no-shards > $O/mc8.json 2> $O/mc8.err &&
 python3 -c "import json; d=json.loads(open('$O/mc8.json').read().strip().splitlines()[-1]); print('mc8', d['legs'].get('cfg3_multi_ctx'))" &&
 for N in 2 8; do
-  timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29560 + N)) bench.py --gpus $N --dist-backend gloo --one-device --steps 10 --warmup 2 --no-cpu-baseline --no-shards > $O/n$N.json 2> $O/n$N.err || exit 1
+  timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29560 + N)) bench.py --full --gpus $N --dist-backend gloo --one-device --steps 10 --warmup 2 --no-cpu-baseline --no-shards > $O/n$N.json 2> $O/n$N.err || exit 1
   python3 -c "import json; d=json.loads(open('$O/n$N.json').read().strip().splitlines()[-1]); print('N=$N', d['value'], d['scaling'], d['config']['n_total'], d['config'].get('config_file'), d['parity_vs_reference'], {k: (v.get('M'), v.get('ok')) for k, v in d['legs'].items()})"
 done
 echo "rc=$?"

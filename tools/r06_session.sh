@@ -14,5 +14,5 @@ echo "pytest ok $(date +%T) $(tail -1 $O/pytest_gpu.txt)" &&
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 &&
 echo "smoke ok $(date +%T)" || { echo "FAILED $(date +%T)"; tail -30 $O/pytest_gpu.txt; exit 1; }
 fi
-timeout -k 10 600 python3 -u bench.py > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 600 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err &&
 echo "bench ok $(date +%T)" && python3 tools/bench_summary.py $O/bench.json
