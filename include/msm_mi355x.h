@@ -365,6 +365,46 @@ int msm_wbits_ctx_mult(msm_wbits_ctx *ctx, void *ret, const byte *scalars, size_
 size_t msm_wbits_ctx_table_rows(const msm_wbits_ctx *ctx);
 void msm_wbits_ctx_destroy(msm_wbits_ctx *ctx);
 
+/* ---- bulk Jacobian -> affine (replaces ref src/multi_scalar.c:17-62, blst_p{1,2}s_to_affine;
+ * blst.h:222-223, :362; what blst.hpp:389,406,438 calls) ----
+ * dst[i] = the canonical affine form of point i (fully reduced, blst Montgomery
+ * layout; byte-identical to the reference's for finite points).  Named msm_, not
+ * blst_: the reference's own blst_p{1,2}s_to_affine stays global in a caller that
+ * links both libraries; a caller forwards in one line.
+ * msm_p{1,2}s_to_affine: pointer rule of multi_scalar.c:30 (a NULL entry means "the
+ * point right after the previous one", and the array is not read past it: {ptr, NULL}
+ * is one flat array); points and dst in host memory; runs on the current device.
+ * msm_points_to_affine: flat arrays, each side in host or device memory (device
+ * pointers 8-byte aligned), on HIP device `device`.
+ * On the GPU: one batch inversion over each chunk of points (default 2^18,
+ * MSM_TO_AFFINE_CHUNK=<points> overrides, read at each call), as a tree of products
+ * of 8 (k_ta_up / k_ta_leaf / k_ta_down, csrc/to_affine.hip), about 9.7 field products
+ * per point; device memory is bounded by the chunk, not by npoints; host memory goes
+ * through two pinned staging buffers per direction, copies overlapping the kernels.
+ * Difference, toward the exact result: a point with Z = 0 is infinity whatever its X
+ * and Y hold; its output is the all-zero affine point and no other output is
+ * affected.  (The reference multiplies Z = 0 into the product shared by a stride of
+ * 1536 / 768 points and corrupts all of them, its own comment at multi_scalar.c:14-16;
+ * the same defect the wbits "inf" cases record.)
+ * npoints == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: NULL dst
+ * or source with npoints > 0, group other than 1 or 2, overlapping host ranges.
+ * MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP failure (msm_last_error()); a host
+ * dst is then zero-filled, never half written; a device dst is unspecified.
+ * Streams: the call first waits for the work queued earlier on hip_stream (device
+ * sources are read by kernels ordered on it; for a host source the stream is
+ * drained).  With a device dst the work is ordered on hip_stream and the call may
+ * return before it finishes (hip_stream NULL: it has finished); with a host dst the
+ * call returns with the data there.  Thread-safe per call: each call leases an
+ * engine from the pool keyed by (device, group), released by
+ * msm_release_engine_cache() and counted by msm_engine_cache_stats(). */
+int msm_p1s_to_affine(blst_p1_affine dst[], const blst_p1 *const points[], size_t npoints);
+int msm_p2s_to_affine(blst_p2_affine dst[], const blst_p2 *const points[], size_t npoints);
+int msm_points_to_affine(int group, int device, void *dst_affine, const void *src_jacobian, size_t npoints,
+                         int src_on_device, int dst_on_device, void *hip_stream);
+/* diagnostic: number of product levels (k_ta_up launches) the plan uses above the
+ * points of one chunk for this n */
+int msm_to_affine_levels(size_t npoints);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

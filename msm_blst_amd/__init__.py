@@ -11,6 +11,7 @@ Mirrors:
   ches.CHESContext                                    ref main_p1.cpp CHES driver (see ches.py)
   bgmw.BGMWContext                                    ref main_p1.cpp BGMW95 driver (see bgmw.py)
   wbits.WbitsContext, wbits.precompute / wbits.mult   blst_p{1,2}s_mult_wbits[_precompute] (see wbits.py)
+  ps_to_affine                                        blst_p{1,2}s_to_affine (ref multi_scalar.c:17-62), bulk, on the GPU
 """
 import ctypes
 
@@ -20,7 +21,7 @@ from .ches import CHESContext
 from .wbits import WbitsContext
 
 __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext", "p1s_mult_pippenger", "p2s_mult_pippenger", "ps_add", "fixed_points", "gen_scalars",
-           "compress", "to_affine", "device_count", "lib"]
+           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
 JAC_BYTES = {1: 144, 2: 288}
@@ -76,6 +77,36 @@ def to_affine(group, jac):
     out = (ctypes.c_uint8 * POINT_BYTES[group])()
     getattr(lib(), f"msm_p{group}_to_affine")(out, _buf(jac))
     return bytes(out)
+
+
+def ps_to_affine(group, jacobians, n, *, src_on_device=False, dst=None, device=0, stream=None):
+    """n Jacobians (blst_p1 / blst_p2 layout, 144 / 288 B each) -> n affine points
+    (msm_points_to_affine; Z = 0 gives the all-zero point).  A host source is a
+    bytes-like object, a device source (src_on_device) a device pointer.  Without
+    dst the result comes back as bytes; with dst=<device pointer> it is written
+    there, ordered on `stream`, and None is returned."""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if src_on_device:
+        src = jacobians
+    else:
+        src = _buf(jacobians)
+        have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+        if have < n * JAC_BYTES[group]:
+            raise ValueError(f"{have} bytes of Jacobians given, {n * JAC_BYTES[group]} needed")
+    if dst is not None:
+        check(lib().msm_points_to_affine(group, device, dst, src, n, int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (POINT_BYTES[group] * n))()
+    check(lib().msm_points_to_affine(group, device, out, src, n, int(bool(src_on_device)), 0, stream))
+    return bytes(out)
+
+
+def to_affine_levels(n):
+    """Product levels of the batch inversion above n points (msm_to_affine_levels)."""
+    return lib().msm_to_affine_levels(n)
 
 
 def _mult(group, points, scalars, n, nbits):

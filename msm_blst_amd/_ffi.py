@@ -123,6 +123,10 @@ def lib():
     for g in (1, 2):
         getattr(L, f"blst_p{g}s_add").argtypes = [vp, vp, sz]
         getattr(L, f"blst_p{g}s_add").restype = None
+    for g in (1, 2):
+        getattr(L, f"msm_p{g}s_to_affine").argtypes = [vp, vp, sz]
+    L.msm_points_to_affine.argtypes = [i32, i32, vp, vp, sz, i32, i32, vp]
+    L.msm_to_affine_levels.argtypes = [sz]
     _lib = L
     return L
 

@@ -22,6 +22,7 @@
 #include "pool.hpp"
 #include "ptr_walk.hpp"
 #include "table_registry.hpp"
+#include "to_affine.hpp"
 
 using namespace msm;
 
@@ -289,6 +290,63 @@ void wbits_mult(void *ret, const void *table, size_t wbits, size_t n, const byte
     (*eng)->run(s, nullptr, nb, (int)nbits, &out);
   }
   memcpy(ret, &out, sizeof out);
+}
+
+// ---- bulk Jacobian -> affine (ref multi_scalar.c:17-62) ----
+// runs: the host source as runs of adjacent points (ptr_walk.hpp), or empty
+// with src_dev set.  cs orders the kernels: the caller's stream when a side is
+// device memory, else the leased engine's own.
+template <int G>
+void points_to_affine(int dev, void *dst, const void *src_dev_ptr,
+                      const std::vector<typename ToAffine<G>::Run> &runs, size_t n, bool src_dev, bool dst_dev,
+                      hipStream_t user) {
+  DeviceGuard g(dev);
+  // work queued earlier on the caller's stream may still be writing the source:
+  // device sources are read by kernels ordered on that stream; host sources are
+  // read by this thread, so the stream is drained first
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+  auto eng = EnginePool<ToAffine<G>>::get().lease(dev, G, [&] { return std::make_unique<ToAffine<G>>(dev); });
+  const bool on_user = src_dev || dst_dev;
+  hipStream_t cs = on_user ? user : eng->stream();
+  (*eng)->run(cs, src_dev_ptr, runs, dst, n, src_dev, dst_dev);
+  // the legacy default stream gives the caller nothing to wait on: finish here
+  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+constexpr int kCurrentDevice = -0x7fffffff;  // the blst-style calls: hipGetDevice
+
+bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bn && y < x + an;
+}
+
+template <int G>
+int points_to_affine_checked(int dev, void *dst, const void *src_flat, const void *const *ptrs, size_t n,
+                             bool src_dev, bool dst_dev, hipStream_t user) {
+  typedef typename ToAffine<G>::Run Run;
+  std::vector<Run> runs;
+  if (!src_dev) {
+    if (ptrs) walk_runs(ptrs, n, 144 * G, [&](size_t i, const uint8_t *p, size_t k) { runs.push_back(Run{i, p, k}); });
+    else runs.push_back(Run{0, (const uint8_t *)src_flat, n});
+    for (const Run &r : runs) {
+      if (!r.p) return fail(MSM_E_ARG, "null point pointer");
+      if (!dst_dev && ranges_overlap(r.p, r.count * 144 * G, dst, n * 96 * G))
+        return fail(MSM_E_ARG, "source and destination overlap");
+    }
+  } else if (((uintptr_t)src_flat & 7) != 0) {
+    return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  }
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev == kCurrentDevice ? ndev < 1 : (dev < 0 || dev >= ndev)) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    if (dev == kCurrentDevice) MSM_HIP_CHECK(hipGetDevice(&dev));
+    points_to_affine<G>(dev, dst, src_flat, runs, n, src_dev, dst_dev, user);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (!dst_dev) memset(dst, 0, n * 96 * G);  // never half written
+    return fail(MSM_E_HIP, e.what());
+  }
 }
 
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
@@ -618,6 +676,35 @@ MSM_POINTS_ADD(2)
 MSM_WBITS_ENTRIES(1, 8192)  /* SCRATCH_SZ of ref multi_scalar.c:78 */
 MSM_WBITS_ENTRIES(2, 4096)
 #undef MSM_WBITS_ENTRIES
+
+// ---- bulk Jacobian -> affine (replaces ref multi_scalar.c:17-62) ----
+// pointer rule of multi_scalar.c:30 (walk_runs, ptr_walk.hpp); current device
+#define MSM_PS_TO_AFFINE(g)                                                                                       \
+  int msm_p##g##s_to_affine(blst_p##g##_affine dst[], const blst_p##g *const points[], size_t npoints) {        \
+    if (npoints == 0) return MSM_OK;                                                                              \
+    if (!dst || !points || !points[0]) return fail(MSM_E_ARG, "null dst / points");                               \
+    return points_to_affine_checked<g>(kCurrentDevice, dst, nullptr, (const void *const *)points, npoints, false, \
+                                       false, nullptr);                                                           \
+  }
+MSM_PS_TO_AFFINE(1)
+MSM_PS_TO_AFFINE(2)
+#undef MSM_PS_TO_AFFINE
+
+int msm_points_to_affine(int group, int device, void *dst, const void *src, size_t npoints, int src_on_device,
+                         int dst_on_device, void *hip_stream) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (npoints == 0) return MSM_OK;
+  if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
+  if (npoints > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
+  if (device == kCurrentDevice) return fail(MSM_E_NODEV, "no such HIP device");
+  if (group == 1)
+    return points_to_affine_checked<1>(device, dst, src, nullptr, npoints, src_on_device != 0, dst_on_device != 0,
+                                       (hipStream_t)hip_stream);
+  return points_to_affine_checked<2>(device, dst, src, nullptr, npoints, src_on_device != 0, dst_on_device != 0,
+                                     (hipStream_t)hip_stream);
+}
+
+int msm_to_affine_levels(size_t npoints) { return (int)ta_levels(std::min(npoints, ta_chunk())).size(); }
 
 const char *msm_last_error(void) { return g_err.c_str(); }
 

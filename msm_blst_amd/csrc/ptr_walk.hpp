@@ -45,4 +45,32 @@ inline const uint8_t *contiguous(std::vector<uint8_t> &buf, const void *const *p
   return buf.data();
 }
 
+// The same rule as a list of runs, for callers that stage the elements chunk by
+// chunk instead of gathering all of them at once: fn(first index, pointer,
+// count) for every maximal run of adjacent elements, in order.  A NULL entry
+// ends the walk of the array: everything left continues the current run (the
+// reference never advances past a NULL, ref multi_scalar.c:30).
+template <class Fn>
+inline void walk_runs(const void *const *ptrs, size_t n, size_t sz, Fn fn) {
+  if (n == 0) return;
+  const void *const *pp = ptrs;
+  const uint8_t *run = (const uint8_t *)*pp++;
+  size_t i = 0, k = 1;
+  while (i + k < n) {
+    if (!*pp) {
+      k = n - i;
+      break;
+    }
+    if ((const uint8_t *)*pp == run + k * sz) {
+      ++k, ++pp;
+      continue;
+    }
+    fn(i, run, k);
+    i += k;
+    run = (const uint8_t *)*pp++;
+    k = 1;
+  }
+  fn(i, run, k);
+}
+
 }  // namespace msm

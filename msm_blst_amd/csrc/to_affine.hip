@@ -1,0 +1,380 @@
+// to_affine.hip -- bulk Jacobian -> affine normalisation on one MI355X
+// (replaces ref src/multi_scalar.c:17-62, blst_p{1,2}s_to_affine; declared at
+// ref bindings/blst.h:222-223, :362; used by bindings/blst.hpp:389,406,438).
+//
+// The reference shares one inversion over a stride of 1536 / 768 points with a
+// serial prefix-product walk.  Here the whole chunk shares the inversions of
+// its top level (at most TA_LEAF), through a tree of products (to_affine.hpp:
+// TA_K = 8 elements per group):
+//   k_ta_up    lane t: level[l+1][t] = prod of level[l][8t .. 8t+7]
+//   k_ta_leaf  one Fermat inversion per element of the top level
+//   k_ta_down  lane t: from 1 / level[l+1][t] and its group's 8 elements, every
+//              element's inverse (prefix products recomputed into registers,
+//              then back-substitution), written in place over level[l]
+// Level 0 is the Z coordinates, read straight from the blst Jacobians, and the
+// level-0 k_ta_down writes the blst affine output.
+//
+// No layout conversion per coordinate: the stored limbs of a blst coordinate
+// (v 2^384 mod p) are used AS the internal value (internal Montgomery R =
+// 2^392, so they stand for v 2^-8).  The tree then yields (Z 2^-8)^-1; one
+// product with 2^-8 (FROMINT28) gives zi = 1/Z in internal form, and
+// fp_mul(X limbs, zi^2) = X zi^2 2^384 is already the blst form of x.
+// Products per point: 1 (up) + 1 (prefix) + 2 (back-substitution) + 1 (2^-8)
+// + 4 (zi^2, zi^3, x, y) = 9 at level 0, plus 4 / 7 for the levels above
+// (4 per element, n / 7 elements) and 570 / 8^levels for the leaves: ~9.7.
+//
+// A zero Z (infinity, whatever X and Y hold) enters the products as one and
+// its output is the all-zero point; no other output is affected.  (The
+// reference multiplies the zero into the shared product and corrupts the
+// whole stride, ref multi_scalar.c:14-16.)
+//
+// G2 runs on lane pairs (Fp2L, fp2l.hpp; as k_ches_table2p / k_wbits_table2p):
+// the seven prefix products alone are 7 x 28 = 196 registers for a one-lane
+// Fp2, before the operands and temporaries of an Fp2 product (the one-lane
+// k_wbits_table<2> spilled with far less live state); a lane of a pair holds
+// one component, the register use of the G1 kernel.
+#include "to_affine.hpp"
+
+#include <cstring>
+#include <type_traits>
+
+#include "pair_kernels.hpp"
+
+#ifndef MSM_GROUP
+#error "define MSM_GROUP (1 or 2)"
+#endif
+
+namespace msm {
+
+template <int G>
+struct TaLane;
+template <>
+struct TaLane<1> {
+  typedef Fp LF;
+};
+template <>
+struct TaLane<2> {
+  typedef Fp2L LF;
+};
+
+// level elements (internal limbs, 56 B per component, 8-B aligned)
+__device__ __forceinline__ void ta_ld(Fp &r, const Fp *p, int) {
+  const uint2 *s = reinterpret_cast<const uint2 *>(p);
+#pragma unroll
+  for (int i = 0; i < NL / 2; ++i) {
+    const uint2 v = s[i];
+    r.v[2 * i] = v.x;
+    r.v[2 * i + 1] = v.y;
+  }
+}
+__device__ __forceinline__ void ta_ld(Fp2L &r, const Fp2 *p, int comp) { ld_comp(r.c, p, comp); }
+__device__ __forceinline__ void ta_st(Fp *p, const Fp &a, int) {
+  uint2 *d = reinterpret_cast<uint2 *>(p);
+#pragma unroll
+  for (int i = 0; i < NL / 2; ++i) d[i] = make_uint2(a.v[2 * i], a.v[2 * i + 1]);
+}
+__device__ __forceinline__ void ta_st(Fp2 *p, const Fp2L &a, int comp) { st_comp(p, a.c, comp); }
+// one blst coordinate (6 G limbs of 64 bits), limbs taken as they are
+__device__ __forceinline__ void ta_ld_raw(Fp &r, const uint64_t *l, int) { unpack384(r, l); }
+__device__ __forceinline__ void ta_ld_raw(Fp2L &r, const uint64_t *l, int comp) { unpack384(r.c, l + 6 * comp); }
+__device__ __forceinline__ void ta_st_raw(uint64_t *l, const Fp &a, int) { pack384(l, a); }
+__device__ __forceinline__ void ta_st_raw(uint64_t *l, const Fp2L &a, int comp) { pack384(l + 6 * comp, a.c); }
+// a 2^-8 (the internal form of 2^-8 is 2^384 mod p = FROMINT28)
+__device__ __forceinline__ void ta_mulk(Fp &r, const Fp &a) {
+  Fp k;
+  fp_set(k, FROMINT28);
+  fp_mul(r, a, k);
+}
+__device__ __forceinline__ void ta_mulk(Fp2L &r, const Fp2L &a) { ta_mulk(r.c, a.c); }
+__device__ __forceinline__ void ta_sel(Fp &r, bool c, const Fp &a) {  // r = c ? a : r
+#pragma unroll
+  for (int i = 0; i < NL; ++i) r.v[i] = c ? a.v[i] : r.v[i];
+}
+__device__ __forceinline__ void ta_sel(Fp2L &r, bool c, const Fp2L &a) { ta_sel(r.c, c, a.c); }
+
+template <int J, int N, class Fn>
+__device__ __forceinline__ void ta_static_for(Fn &&f) {
+  if constexpr (J < N) {
+    f(std::integral_constant<int, J>{});
+    ta_static_for<J + 1, N>(f);
+  }
+}
+
+// element j of a level: L0 = the Z of Jacobian j (zero -> one, `zero` set;
+// uniform over a lane pair), else level element j
+template <int G, bool L0>
+__device__ __forceinline__ void ta_elem(typename TaLane<G>::LF &r, const void *lvl, size_t j, int comp, bool &zero) {
+  typedef typename TaLane<G>::LF LF;
+  if (L0) {
+    ta_ld_raw(r, static_cast<const uint64_t *>(lvl) + j * 18 * G + 12 * G, comp);
+    zero = f_is_zero_exact(r);
+    LF one;
+    f_one(one);
+    ta_sel(r, zero, one);
+  } else {
+    ta_ld(r, static_cast<const typename FieldOf<G>::F *>(lvl) + j, comp);
+    zero = false;
+  }
+}
+
+// lane (pair) t < n_dst: dst[t] = prod src[8t .. min(8t + 8, n_src))
+template <int G, bool L0>
+static __global__ void __launch_bounds__(128)
+    k_ta_up(const void *__restrict__ src, size_t n_src, typename FieldOf<G>::F *__restrict__ dst, size_t n_dst) {
+  typedef typename TaLane<G>::LF LF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= n_dst) return;  // whole pairs only
+  const size_t j0 = t * TA_K;
+  const size_t cnt = min((size_t)TA_K, n_src - j0);
+  bool z;
+  LF acc;
+  ta_elem<G, L0>(acc, src, j0, comp, z);
+  for (size_t j = 1; j < cnt; ++j) {
+    LF e;
+    ta_elem<G, L0>(e, src, j0 + j, comp, z);
+    f_mul_bs(acc, acc, e);
+  }
+  ta_st(dst + t, acc, comp);
+}
+
+// top level, in place: top[t] = 1 / top[t]
+template <int G>
+static __global__ void __launch_bounds__(64) k_ta_leaf(typename FieldOf<G>::F *top, size_t m) {
+  typedef typename TaLane<G>::LF LF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= m) return;
+  LF a, r;
+  ta_ld(a, top + t, comp);
+  f_inv(r, a);
+  ta_st(top + t, r, comp);
+}
+
+// lane (pair) t < n_up: inv_up[t] = 1 / prod lvl[8t ..]; every element of the
+// group is replaced by its inverse (L0: the affine point of Jacobian j is
+// written to out instead, lvl = the Jacobians, read only)
+template <int G, bool L0>
+static __global__ void __launch_bounds__(128)
+    k_ta_down(const typename FieldOf<G>::F *__restrict__ inv_up, size_t n_up, void *lvl, size_t n_lvl,
+              uint64_t *out) {
+  typedef typename TaLane<G>::LF LF;
+  typedef typename FieldOf<G>::F SF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= n_up) return;
+  const size_t j0 = t * TA_K;
+  const int cnt = (int)min((size_t)TA_K, n_lvl - j0);
+  LF I;
+  ta_ld(I, inv_up + t, comp);
+  bool z;
+  LF pre[TA_K - 1];  // pre[j] = e_0 .. e_j
+  ta_elem<G, L0>(pre[0], lvl, j0, comp, z);
+  // (compile-time steps: a `#pragma unroll` loop guarded by j < cnt is turned
+  // into a loop of cnt trips, not unrolled, and pre[] lands in scratch)
+  ta_static_for<1, (int)TA_K - 1>([&](auto jc) __attribute__((always_inline)) {
+    constexpr int j = decltype(jc)::value;
+    if (j < cnt) {
+      LF e;
+      ta_elem<G, L0>(e, lvl, j0 + j, comp, z);
+      f_mul_bs(pre[j], pre[j - 1], e);
+    }
+  });
+  ta_static_for<0, (int)TA_K>([&](auto jc) __attribute__((always_inline)) {
+    constexpr int j = (int)TA_K - 1 - decltype(jc)::value;
+    if (j < cnt) {
+      LF e, ij;
+      ta_elem<G, L0>(e, lvl, j0 + j, comp, z);
+      if constexpr (j > 0) {
+        f_mul_bs(ij, I, pre[j - 1]);  // 1 / e_j = (1 / (e_0 .. e_j)) (e_0 .. e_{j-1})
+        f_mul_bs(I, I, e);
+      } else {
+        ij = I;
+      }
+      if constexpr (L0) {
+        const uint64_t *P = static_cast<const uint64_t *>(lvl) + (j0 + j) * 18 * G;
+        uint64_t *o = out + (j0 + j) * 12 * G;
+        LF zi, zi2, zi3, X, Y, zero;
+        ta_mulk(zi, ij);
+        f_sqr(zi2, zi);
+        f_mul_bs(zi3, zi2, zi);
+        ta_ld_raw(X, P, comp);
+        ta_ld_raw(Y, P + 6 * G, comp);
+        f_mul_bs(X, X, zi2);
+        f_mul_bs(Y, Y, zi3);
+        f_csub(X);
+        f_csub(Y);
+        f_zero(zero);
+        ta_sel(X, z, zero);
+        ta_sel(Y, z, zero);
+        ta_st_raw(o, X, comp);
+        ta_st_raw(o + 6 * G, Y, comp);
+      } else {
+        ta_st(static_cast<SF *>(lvl) + j0 + j, ij, comp);
+      }
+    }
+  });
+}
+
+template <int G>
+ToAffine<G>::ToAffine(int device) : dev_(device) {
+  DeviceGuard g(dev_);
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
+  }
+  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
+}
+
+template <int G>
+ToAffine<G>::~ToAffine() {
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(dev_);
+  // queued work may still read the staging and level buffers
+  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
+  if (h2d_) (void)hipStreamSynchronize(h2d_);
+  if (d2h_) (void)hipStreamSynchronize(d2h_);
+  for (int i = 0; i < 2; ++i) {
+    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
+    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
+    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
+    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
+    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
+    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
+  }
+  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
+  if (h2d_) (void)hipStreamDestroy(h2d_);
+  if (d2h_) (void)hipStreamDestroy(d2h_);
+  if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+template <int G>
+void ToAffine<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
+  if (bytes <= have) return;
+  for (int i = 0; i < 2; ++i) {
+    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
+    slots[i] = nullptr;
+  }
+  have = 0;
+  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
+  have = bytes;
+}
+
+// one chunk, device to device: n <= the chunk the level buffer was sized for
+template <int G>
+void ToAffine<G>::kernels(hipStream_t s, const void *d_src, void *d_dst, size_t n) {
+  typedef typename FieldOf<G>::F SF;
+  const std::vector<size_t> lv = ta_levels(n);
+  std::vector<SF *> L(lv.size());
+  size_t off = 0;
+  for (size_t i = 0; i < lv.size(); ++i) {
+    L[i] = lv_.as<SF>() + off;
+    off += lv[i];
+  }
+  if (off * sizeof(SF) > lv_.bytes) throw std::runtime_error("to_affine: level buffer too small");
+  const unsigned B = 128;
+  hipLaunchKernelGGL((k_ta_up<G, true>), dim3(nblk(lv[0] * G, B)), dim3(B), 0, s, d_src, n, L[0], lv[0]);
+  MSM_HIP_CHECK(hipGetLastError());
+  for (size_t i = 1; i < lv.size(); ++i) {
+    hipLaunchKernelGGL((k_ta_up<G, false>), dim3(nblk(lv[i] * G, B)), dim3(B), 0, s, (const void *)L[i - 1],
+                       lv[i - 1], L[i], lv[i]);
+    MSM_HIP_CHECK(hipGetLastError());
+  }
+  const size_t top = lv.size() - 1;
+  hipLaunchKernelGGL(k_ta_leaf<G>, dim3(nblk(lv[top] * G, 64)), dim3(64), 0, s, L[top], lv[top]);
+  MSM_HIP_CHECK(hipGetLastError());
+  for (size_t i = top; i >= 1; --i) {
+    hipLaunchKernelGGL((k_ta_down<G, false>), dim3(nblk(lv[i] * G, B)), dim3(B), 0, s, (const SF *)L[i], lv[i],
+                       (void *)L[i - 1], lv[i - 1], (uint64_t *)nullptr);
+    MSM_HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL((k_ta_down<G, true>), dim3(nblk(lv[0] * G, B)), dim3(B), 0, s, (const SF *)L[0], lv[0],
+                     const_cast<void *>(d_src), n, static_cast<uint64_t *>(d_dst));
+  MSM_HIP_CHECK(hipGetLastError());
+}
+
+template <int G>
+void ToAffine<G>::run(hipStream_t cs, const void *src_dev_ptr, const std::vector<Run> &runs, void *dst, size_t n,
+                      bool src_dev, bool dst_dev) {
+  typedef typename FieldOf<G>::F SF;
+  static_assert(sizeof(SF) == ELEM, "level element size");
+  if (!n) return;
+  DeviceGuard g(dev_);
+  const size_t C = std::min(n, ta_chunk());
+  size_t elems = 0;
+  for (size_t v : ta_levels(C)) elems += v;
+  lv_.ensure(elems * ELEM);
+  if (!src_dev) {
+    ensure_pinned(pin_in_, pin_in_bytes_, C * JAC);
+    din_[0].ensure(C * JAC);
+    din_[1].ensure(C * JAC);
+  }
+  if (!dst_dev) {
+    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
+    dout_[0].ensure(C * AFF);
+    dout_[1].ensure(C * AFF);
+  }
+  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the level buffers of the previous call
+  size_t ri = 0, roff = 0;                             // gather cursor: run, point within it
+  struct Pending {
+    int slot;
+    size_t off, cnt;
+  } prev{0, 0, 0};
+  auto drain = [&](const Pending &p) {
+    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
+    memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
+  };
+  size_t k = 0;
+  for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
+    const size_t cnt = std::min(C, n - c0);
+    const int slot = (int)(k & 1);
+    const void *d_src;
+    void *d_dst;
+    if (!src_dev) {
+      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
+      uint8_t *w = static_cast<uint8_t *>(pin_in_[slot]);
+      for (size_t left = cnt; left;) {  // the gather writes straight into pinned memory
+        if (ri >= runs.size()) throw std::runtime_error("to_affine: pointer runs do not cover the points");
+        const size_t take = std::min(left, runs[ri].count - roff);
+        memcpy(w, runs[ri].p + roff * JAC, take * JAC);
+        w += take * JAC, left -= take, roff += take;
+        if (roff == runs[ri].count) ++ri, roff = 0;
+      }
+      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
+      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], cnt * JAC, hipMemcpyHostToDevice, h2d_));
+      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
+      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
+      d_src = din_[slot].p;
+    } else {
+      d_src = static_cast<const uint8_t *>(src_dev_ptr) + c0 * JAC;
+    }
+    if (!dst_dev) {
+      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
+      d_dst = dout_[slot].p;
+    } else {
+      d_dst = static_cast<uint8_t *>(dst) + c0 * AFF;
+    }
+    kernels(cs, d_src, d_dst, cnt);
+    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    if (!dst_dev) {
+      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
+      MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * AFF, hipMemcpyDeviceToHost, d2h_));
+      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
+      if (k) drain(prev);  // chunk k - 1, while chunk k runs
+      prev = Pending{slot, c0, cnt};
+    }
+  }
+  if (!dst_dev) drain(prev);
+  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+}
+
+template class ToAffine<MSM_GROUP>;
+
+}  // namespace msm

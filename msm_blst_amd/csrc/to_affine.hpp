@@ -1,0 +1,86 @@
+// to_affine.hpp -- bulk Jacobian -> affine normalisation on the GPU
+// (replaces ref src/multi_scalar.c:17-62, blst_p{1,2}s_to_affine; kernels and
+// orchestration in to_affine.hip).  This header is host-only: the plan (level
+// sizes, chunk size) is shared with abi.cpp's msm_to_affine_levels().
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <vector>
+
+#include "engine.hpp"
+
+namespace msm {
+
+// Hierarchical Montgomery batch inversion: a lane of k_ta_up multiplies TA_K
+// consecutive elements of a level into one element of the next, until a level
+// has at most TA_LEAF elements; those are inverted one per lane (k_ta_leaf)
+// and k_ta_down walks back.  K = 8 keeps the K - 1 prefix products of a group
+// in registers (7 x 14 VGPRs; K = 16 would need 210 and spill).
+// Level sizes for one default chunk of 2^18 points: 32768, 4096, 512, 64
+// (4 levels); a 2^20 input is four such chunks.
+constexpr size_t TA_K = 8;
+constexpr size_t TA_LEAF = 256;
+constexpr size_t TA_CHUNK_DEFAULT = (size_t)1 << 18;
+
+// points per chunk: MSM_TO_AFFINE_CHUNK=<points> overrides the default, read at each call
+inline size_t ta_chunk() {
+  const char *e = getenv("MSM_TO_AFFINE_CHUNK");
+  if (e && *e) {
+    const long long v = atoll(e);
+    if (v > 0) return (size_t)v;
+  }
+  return TA_CHUNK_DEFAULT;
+}
+
+// sizes of the levels above n points (at least one level for n >= 1)
+inline std::vector<size_t> ta_levels(size_t n) {
+  std::vector<size_t> lv;
+  while (n) {
+    n = (n + TA_K - 1) / TA_K;
+    lv.push_back(n);
+    if (n <= TA_LEAF) break;
+  }
+  return lv;
+}
+
+// One engine: level buffers, and for host memory two pinned + two device
+// staging buffers per direction with their own copy streams.
+template <int G>
+class ToAffine {
+ public:
+  static constexpr size_t JAC = 144 * G, AFF = 96 * G, ELEM = 56 * G;
+  // runs [first index, pointer, count] of a blst pointer array (ptr_walk.hpp)
+  struct Run {
+    size_t first;
+    const uint8_t *p;
+    size_t count;
+  };
+  explicit ToAffine(int device);
+  ~ToAffine();
+  ToAffine(const ToAffine &) = delete;
+  ToAffine &operator=(const ToAffine &) = delete;
+  // n Jacobians -> n affine points.  src: device memory (src_dev), or host
+  // memory named by `runs` (ascending, covering [0, n)).  dst: flat, host or
+  // device.  `cs` orders the kernels (the caller's stream when a side is device
+  // memory, else the engine's).  Device destination: returns with the work
+  // queued on cs; host destination: returns with the data in dst.
+  void run(hipStream_t cs, const void *src_dev_ptr, const std::vector<Run> &runs, void *dst, size_t n, bool src_dev,
+           bool dst_dev);
+  size_t device_bytes() const { return lv_.bytes + din_[0].bytes + din_[1].bytes + dout_[0].bytes + dout_[1].bytes; }
+  int device() const { return dev_; }
+
+ private:
+  int dev_;
+  DevBuf lv_, din_[2], dout_[2];
+  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr};
+  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0;
+  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
+  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
+  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (level buffers are reused)
+  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  void kernels(hipStream_t s, const void *d_src, void *d_dst, size_t n);
+};
+
+}  // namespace msm
