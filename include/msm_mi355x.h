@@ -405,6 +405,47 @@ int msm_points_to_affine(int group, int device, void *dst_affine, const void *sr
  * points of one chunk for this n */
 int msm_to_affine_levels(size_t npoints);
 
+/* ---- bulk point decoding (replaces the reference's one-point blst_p{1,2}_uncompress,
+ * blst_p{1,2}_deserialize and blst_p{1,2}_affine_in_g{1,2}: ref src/e1.c:236-351,
+ * src/e2.c:279-410, src/map_to_g1.c:531-559, src/map_to_g2.c:403-443) ----
+ * src: npoints ZCash-encoded entries of 48 G bytes (MSM_ENC_COMPRESSED) or 96 G bytes
+ * (MSM_ENC_SERIALIZED), G = group.  Entry i is decoded as the reference decodes it: an
+ * entry of a serialized array whose compressed bit is set has its first 48 G bytes
+ * decoded as a compressed point; infinity is c0 00.. / 40 00...
+ * status[i] is the reference's return code: 0 success, 1 bad encoding, 2 not on the
+ * curve, 3 not in the group (the reference itself: only G1 x = 0).  With
+ * MSM_DECODE_CHECK_GROUP an entry that would be 0 and lies outside the prime-order
+ * subgroup (blst_p{1,2}_affine_in_g{1,2} false) gets 3; infinity passes.
+ * dst[i] of a status-0 entry is the canonical affine point in blst Montgomery layout,
+ * byte-identical to the reference's (infinity: all zero).  Difference, toward safety:
+ * dst[i] of every entry with a non-zero status is the all-zero point (the reference
+ * leaves its output untouched, or for G1 x = 0 written), so a failed point can enter
+ * an MSM only as the identity.
+ * status and nbad are host memory and may be NULL; nbad receives the number of
+ * non-zero statuses.  src and dst each in host or device memory (device src 4-byte,
+ * device dst 8-byte aligned), on HIP device `device`.
+ * npoints == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: NULL dst
+ * or src with npoints > 0, group other than 1 or 2, unknown encoding, unknown flag
+ * bits, overlapping host ranges.  MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP
+ * failure; a host dst is then zero-filled and status, if given, filled with 1.
+ * Streams as msm_points_to_affine; in addition a call with status or nbad returns
+ * only when they are written.  On the GPU: csrc/decode.hip, chunks of at most 2^18
+ * entries (MSM_DECODE_CHUNK=<entries> overrides, read at each call), host memory
+ * through two pinned staging buffers per direction.  Thread-safe per call (an engine
+ * pool keyed by (device, group), counted by msm_engine_cache_stats(), freed by
+ * msm_release_engine_cache()). */
+enum { MSM_ENC_COMPRESSED = 0, MSM_ENC_SERIALIZED = 1 }; /* stride 48 G / 96 G bytes per entry */
+enum { MSM_DECODE_CHECK_GROUP = 1 };                     /* flags */
+int msm_points_decode(int group, int device, void *dst_affine, uint8_t *status, size_t *nbad, const void *src,
+                      size_t npoints, int encoding, int flags, int src_on_device, int dst_on_device,
+                      void *hip_stream);
+/* decode into a device buffer the context owns, then msm_ctx_set_points(.., on device).
+ * Any non-zero status: the context keeps its previous points, MSM_E_ARG is returned,
+ * *first_bad (may be NULL) is the lowest failing index and msm_last_error() names
+ * index and status. */
+int msm_ctx_set_points_encoded(msm_ctx *ctx, const void *src, size_t npoints, int encoding, int flags,
+                               int src_on_device, size_t *first_bad, void *hip_stream);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

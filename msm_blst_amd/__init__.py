@@ -12,6 +12,8 @@ Mirrors:
   bgmw.BGMWContext                                    ref main_p1.cpp BGMW95 driver (see bgmw.py)
   wbits.WbitsContext, wbits.precompute / wbits.mult   blst_p{1,2}s_mult_wbits[_precompute] (see wbits.py)
   ps_to_affine                                        blst_p{1,2}s_to_affine (ref multi_scalar.c:17-62), bulk, on the GPU
+  ps_decode, MSMContext.set_points_encoded            blst_p{1,2}_uncompress / _deserialize / _affine_in_g{1,2}
+                                                      (ref e1.c:236-351, e2.c:279-410), bulk, on the GPU
 """
 import ctypes
 
@@ -21,10 +23,12 @@ from .ches import CHESContext
 from .wbits import WbitsContext
 
 __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext", "p1s_mult_pippenger", "p2s_mult_pippenger", "ps_add", "fixed_points", "gen_scalars",
-           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "device_count", "lib"]
+           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
 JAC_BYTES = {1: 144, 2: 288}
+ENC_COMPRESSED, ENC_SERIALIZED = 0, 1  # MSM_ENC_*: 48 G / 96 G bytes per entry
+DECODE_CHECK_GROUP = 1                 # MSM_DECODE_CHECK_GROUP
 
 
 def device_count():
@@ -104,6 +108,43 @@ def ps_to_affine(group, jacobians, n, *, src_on_device=False, dst=None, device=0
     return bytes(out)
 
 
+def _encoded(group, data, n, compressed, on_device):
+    """(pointer or ctypes buffer, encoding) of n encoded entries; a short host buffer raises"""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if on_device:
+        return data, ENC_COMPRESSED if compressed else ENC_SERIALIZED
+    src = _buf(data)
+    have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+    need = n * 48 * group * (1 if compressed else 2)
+    if have < need:
+        raise ValueError(f"{have} bytes of encoded points given, {need} needed")
+    return src, ENC_COMPRESSED if compressed else ENC_SERIALIZED
+
+
+def ps_decode(group, data, n, *, compressed=True, check_group=True, src_on_device=False, dst=None, device=0,
+              stream=None):
+    """n ZCash-encoded points (48 G bytes each compressed, 96 G serialized) -> (affine
+    bytes, status bytes) through msm_points_decode: status 0 ok, 1 bad encoding, 2 not
+    on the curve, 3 not in the group; the affine point of every failed entry is all
+    zero.  check_group adds the subgroup test.  A host source is a bytes-like object,
+    a device source (src_on_device) a device pointer.  With dst=<device pointer> the
+    points are written there, ordered on `stream`, and (None, status bytes) is returned."""
+    src, enc = _encoded(group, data, n, compressed, src_on_device)
+    flags = DECODE_CHECK_GROUP if check_group else 0
+    status = (ctypes.c_uint8 * n)()
+    if dst is not None:
+        check(lib().msm_points_decode(group, device, dst, status, None, src, n, enc, flags, int(bool(src_on_device)), 1,
+                                      stream))
+        return None, bytes(status)
+    out = (ctypes.c_uint8 * (POINT_BYTES[group] * n))()
+    check(lib().msm_points_decode(group, device, out, status, None, src, n, enc, flags, int(bool(src_on_device)), 0,
+                                  stream))
+    return bytes(out), bytes(status)
+
+
 def to_affine_levels(n):
     """Product levels of the batch inversion above n points (msm_to_affine_levels)."""
     return lib().msm_to_affine_levels(n)
@@ -149,10 +190,25 @@ class MSMContext:
         self._ctx = ctypes.c_void_p()
         check(lib().msm_ctx_create(ctypes.byref(self._ctx), group, device, window_bits))
         self.n = 0
+        self.first_bad = None  # index of the entry the last set_points_encoded rejected
 
     def set_points(self, points, n, on_device=False, stream=None):
         ptr = points if on_device else _buf(points)
         check(lib().msm_ctx_set_points(self._ctx, ptr, n, int(bool(on_device)), stream))
+        self.n = n
+
+    def set_points_encoded(self, data, n, compressed=True, check_group=True, on_device=False, stream=None):
+        """Points from n ZCash-encoded entries (see ps_decode), decoded on the GPU into a
+        buffer the context owns.  Any rejected entry raises MsmError (self.first_bad holds
+        its index) and the context keeps its previous points."""
+        src, enc = _encoded(self.group, data, n, compressed, on_device)
+        bad = ctypes.c_size_t(0)
+        self.first_bad = None
+        rc = lib().msm_ctx_set_points_encoded(self._ctx, src, n, enc, DECODE_CHECK_GROUP if check_group else 0,
+                                              int(bool(on_device)), ctypes.byref(bad), stream)
+        if rc != 0 and "rejected" in lib().msm_last_error().decode(errors="replace"):
+            self.first_bad = bad.value
+        check(rc)
         self.n = n
 
     def mult(self, scalars, nbits=255, stride=32, on_device=False, stream=None):

@@ -127,6 +127,8 @@ def lib():
         getattr(L, f"msm_p{g}s_to_affine").argtypes = [vp, vp, sz]
     L.msm_points_to_affine.argtypes = [i32, i32, vp, vp, sz, i32, i32, vp]
     L.msm_to_affine_levels.argtypes = [sz]
+    L.msm_points_decode.argtypes = [i32, i32, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]
+    L.msm_ctx_set_points_encoded.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp]
     _lib = L
     return L
 

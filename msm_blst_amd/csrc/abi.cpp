@@ -17,6 +17,7 @@
 #include <string>
 
 #include "../../include/msm_mi355x.h"
+#include "decode.hpp"
 #include "engine.hpp"
 #include "multi.hpp"
 #include "pool.hpp"
@@ -349,6 +350,61 @@ int points_to_affine_checked(int dev, void *dst, const void *src_flat, const voi
   }
 }
 
+// ---- bulk point decoding (ref e1.c:236-351, e2.c:279-410, map_to_g{1,2}.c in_g{1,2}) ----
+// status: n host bytes or NULL.  cs orders the kernels: the caller's stream when
+// a side is device memory, else the leased engine's own.
+template <int G>
+void points_decode(int dev, void *dst, uint8_t *status, const void *src, size_t n, bool serialized, bool check_group,
+                   bool src_dev, bool dst_dev, hipStream_t user) {
+  DeviceGuard g(dev);
+  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+  auto eng = EnginePool<Decode<G>>::get().lease(dev, G, [&] { return std::make_unique<Decode<G>>(dev); });
+  const bool on_user = src_dev || dst_dev;
+  hipStream_t cs = on_user ? user : eng->stream();
+  (*eng)->run(cs, src, dst, status, n, serialized, check_group, src_dev, dst_dev);
+  // the legacy default stream gives the caller nothing to wait on: finish here
+  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t *nbad, const void *src, size_t n,
+                          int encoding, int flags, bool src_dev, bool dst_dev, hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (encoding != MSM_ENC_COMPRESSED && encoding != MSM_ENC_SERIALIZED) return fail(MSM_E_ARG, "unknown encoding");
+  if (flags & ~MSM_DECODE_CHECK_GROUP) return fail(MSM_E_ARG, "unknown flag bits");
+  if (n == 0) return MSM_OK;  // nothing touched
+  if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
+  if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
+  const bool ser = encoding == MSM_ENC_SERIALIZED;
+  const size_t enc = (size_t)(ser ? 96 : 48) * group, aff = (size_t)96 * group;
+  if (!src_dev && !dst_dev && ranges_overlap(src, n * enc, dst, n * aff))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (status && ((!src_dev && ranges_overlap(src, n * enc, status, n)) ||
+                 (!dst_dev && ranges_overlap(dst, n * aff, status, n))))
+    return fail(MSM_E_ARG, "status overlaps the source or the destination");
+  if (src_dev && ((uintptr_t)src & 3) != 0) return fail(MSM_E_ARG, "device source not 4-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  std::vector<uint8_t> own;  // nbad without status: counted from a buffer of our own
+  uint8_t *st = status;
+  try {
+    if (!st && nbad) {
+      own.resize(n);
+      st = own.data();
+    }
+    if (group == 1) points_decode<1>(dev, dst, st, src, n, ser, (flags & MSM_DECODE_CHECK_GROUP) != 0, src_dev, dst_dev, user);
+    else points_decode<2>(dev, dst, st, src, n, ser, (flags & MSM_DECODE_CHECK_GROUP) != 0, src_dev, dst_dev, user);
+    if (nbad) *nbad = n - (size_t)std::count(st, st + n, (uint8_t)0);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (!dst_dev) memset(dst, 0, n * aff);  // never half written
+    if (status) memset(status, 1, n);
+    if (nbad) *nbad = n;
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   size_t w = 0;
   while (n >>= 1) ++w;
@@ -398,6 +454,7 @@ struct msm_ctx {
   std::unique_ptr<Pippenger<1>> g1;
   std::unique_ptr<Pippenger<2>> g2;
   DevBuf scalars;
+  DevBuf decoded;  // msm_ctx_set_points_encoded: the decoded affine points
 };
 
 namespace {
@@ -706,6 +763,12 @@ int msm_points_to_affine(int group, int device, void *dst, const void *src, size
 
 int msm_to_affine_levels(size_t npoints) { return (int)ta_levels(std::min(npoints, ta_chunk())).size(); }
 
+int msm_points_decode(int group, int device, void *dst, uint8_t *status, size_t *nbad, const void *src, size_t npoints,
+                      int encoding, int flags, int src_on_device, int dst_on_device, void *hip_stream) {
+  return points_decode_checked(group, device, dst, status, nbad, src, npoints, encoding, flags, src_on_device != 0,
+                               dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
 const char *msm_last_error(void) { return g_err.c_str(); }
 
 int msm_set_abort_on_error(int on) { return g_abort_on_error.exchange(on != 0 ? 1 : 0); }
@@ -793,6 +856,29 @@ int msm_ctx_set_points(msm_ctx *ctx, const void *points, size_t n, int on_device
   } catch (const std::exception &e) {
     return fail(MSM_E_HIP, e.what());
   }
+}
+
+int msm_ctx_set_points_encoded(msm_ctx *ctx, const void *src, size_t n, int encoding, int flags, int src_on_device,
+                               size_t *first_bad, void *stream) {
+  if (!ctx || (!src && n)) return fail(MSM_E_ARG, "bad args");
+  if (n == 0) return msm_ctx_set_points(ctx, nullptr, 0, 1, stream);
+  std::vector<uint8_t> st;
+  try {
+    DeviceGuard g(ctx->device);
+    st.resize(n);
+    ctx->decoded.ensure(n * 96 * (size_t)ctx->group);
+  } catch (const std::exception &e) {
+    return fail(MSM_E_HIP, e.what());
+  }
+  const int rc = points_decode_checked(ctx->group, ctx->device, ctx->decoded.p, st.data(), nullptr, src, n, encoding,
+                                       flags, src_on_device != 0, true, (hipStream_t)stream);
+  if (rc != MSM_OK) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (st[i]) {  // the context keeps its previous points
+      if (first_bad) *first_bad = i;
+      return fail(MSM_E_ARG, "encoded point " + std::to_string(i) + " rejected: status " + std::to_string((int)st[i]));
+    }
+  return msm_ctx_set_points(ctx, ctx->decoded.p, n, 1, stream);
 }
 
 int msm_ctx_mult(msm_ctx *ctx, void *ret, const byte *scalars, size_t stride, size_t nbits, int on_device,

@@ -1,0 +1,542 @@
+// decode.hip -- bulk decoding of ZCash-encoded BLS12-381 points on one MI355X
+// (replaces ref src/e1.c:236-351 blst_p1_uncompress / _deserialize,
+// src/e2.c:279-410 the G2 twins, src/map_to_g1.c:531-559 and
+// src/map_to_g2.c:403-443 blst_p{1,2}_affine_in_g{1,2}).
+//
+//   k_decode        entry i -> affine point i (blst layout) + status byte:
+//                   parse (big-endian bytes -> 28-bit limbs, range check
+//                   against p, one product with 2^784 -> internal form),
+//                   a = x^3 + b, y = a^((p+1)/4) by a fixed 2-bit-window chain
+//                   (G2: two such chains over Fp, through the norm), y^2 == a,
+//                   sign from the canonical y against (p-1)/2; serialized
+//                   entries check y^2 == a on the given y instead
+//   k_decode_group  status-0 points only: the reference's endomorphism tests
+//                   (Scott, eprint 2021/1130): G1 [z^2]P == -sigma^2(P), G2
+//                   [|z|]P == -psi(P), |z| = 0xd201000000010000, on ec.hpp's
+//                   xyzz formulas; a failing point gets status 3 and is zeroed
+//
+// Lanes of a wave hold different statuses: every lane runs the same chains and
+// the results are selected at the end (the only wave-level branch skips the
+// square root of a serialized array when no lane of the wave holds a compressed
+// entry).  The output of every failed entry is the all-zero point.
+//
+// G1 runs one lane per point, G2 one lane PAIR per point (Fp2L, fp2l.hpp): a
+// lane holds one component, so both kernels have the register use of G1.  The
+// Fp2 square root needs both components in both lanes (the norm a0^2 + a1^2
+// and the two Fp chains are the same instructions on both lanes).
+//
+// Products per point as built (an fp_mul2 priced 1.5 Fp products, an fp_mul4
+// 2.5; tools/decode_timing.py): G1 decode 546 (the chain: 378 squarings + 159
+// products), group check 1238.5 (127 doublings, 16 mixed additions); G2, both
+// lanes, 2185 and 1604.
+#include "decode.hpp"
+
+#include <cstring>
+
+#include "pair_kernels.hpp"
+
+#ifndef MSM_GROUP
+#error "define MSM_GROUP (1 or 2)"
+#endif
+
+namespace msm {
+
+// (p - 3) / 4, the exponent of the square-root chain: a^((p-3)/4) a = a^((p+1)/4)
+__device__ constexpr uint64_t PM3D4[6] = {0xee7fbfffffffeaaaull, 0x07aaffffac54ffffull, 0xd9cc34a83dac3d89ull,
+                                          0xd91dd2e13ce144afull, 0x92c6e9ed90d2eb35ull, 0x0680447a8e5ff9a6ull};
+// 2^784 mod p: integer limbs -> internal form (R = 2^392) in one product
+MSM_CONST uint32_t DEC_R2[NL] = {0x10370ed, 0x6d1c345, 0xe243d62, 0xec45c53, 0x3b1d65a, 0x093317d, 0xb4f36a0,
+                                 0x5d74088, 0xc10ea72, 0x865d118, 0x7320a75, 0xfd5cd50, 0xcc8a759, 0x000c8d4};
+// 1/2 and 4 in internal form; b = 4 (G1), 4 + 4i (G2)
+MSM_CONST uint32_t DEC_HALF[NL] = {0x1a3fe5c, 0xec00000, 0x001588c, 0x066f369, 0x6390970, 0xc1d1048, 0x01bb34f,
+                                   0x6d07b9f, 0x4d84da1, 0x894bdd8, 0x28aecc7, 0x009653e, 0x32cfe7d, 0x0002bbd};
+MSM_CONST uint32_t DEC_FOUR[NL] = {0xd1ff2e0, 0x6000000, 0x00ac467, 0x3379b48, 0x1c84b80, 0x0e88243, 0x0dd9a7e,
+                                   0x683dcf8, 0x6c26d0b, 0x4a5eec2, 0x457663c, 0x04b29f1, 0x967f3e8, 0x0015de9};
+// (p - 1) / 2, plain integer
+MSM_CONST uint32_t DEC_PM1H[NL] = {0xfffd555, 0xff7ffff, 0x9ffffdc, 0xffff58a, 0xb120f55, 0x507b587, 0xfb39869,
+                                   0x79c2895, 0x23ba5c2, 0xa5d66bb, 0xdd3db21, 0xf34d258, 0x8f51cbf, 0x000d008};
+// sigma^2(x, y) = (beta x, y): the cube root of unity with [z^2]P = (beta x, -y) on G1 (internal form)
+MSM_CONST uint32_t DEC_BETA[NL] = {0xa75929a, 0x681b798, 0x22a3e9d, 0xabc02bf, 0x4e5bb45, 0x55e6e7e, 0x4814117,
+                                   0x6d04f1b, 0xae3387d, 0x54acb0c, 0x0a4c74b, 0x56138b5, 0xb64e066, 0x00076f2};
+// psi(x, y) = (conj(x) cx, conj(y) cy), cx = (1 + i)^-((p-1)/3) = cx1 i, cy = (1 + i)^-((p-1)/2) (internal form)
+MSM_CONST uint32_t DEC_PSI_CX1[NL] = {0x58a1811, 0x96e4867, 0x1d5c11c, 0x543e856, 0x13e6366, 0x4b0fc91, 0xae5efbb,
+                                      0x8680210, 0x9941307, 0xf700269, 0xb02eef7, 0x9086bfc, 0x6855919, 0x001291e};
+MSM_CONST uint32_t DEC_PSI_CY0[NL] = {0xcc17b84, 0xcc5da55, 0x1835de7, 0x3e1e677, 0x9e4ae31, 0x9b9a07a, 0xd662557,
+                                      0xb7f1997, 0x71cc4da, 0xa667f92, 0x65115fe, 0x4a3370c, 0xe5b746a, 0x000d16d};
+MSM_CONST uint32_t DEC_PSI_CY1[NL] = {0x33e2f27, 0x32a25aa, 0x27ca1d2, 0xc1e049e, 0xc3f707a, 0x055ca94, 0x2010b7b,
+                                      0x3b93794, 0xd5a86aa, 0xa544de3, 0x556a044, 0x9c66da5, 0x38ec515, 0x000cea3};
+constexpr uint64_t DEC_Z_ABS = 0xd201000000010000ull;
+
+template <int G>
+struct DecLane;
+template <>
+struct DecLane<1> {
+  typedef Fp LF;
+};
+template <>
+struct DecLane<2> {
+  typedef Fp2L LF;
+};
+__device__ __forceinline__ Fp &dec_c(Fp &a) { return a; }
+__device__ __forceinline__ Fp &dec_c(Fp2L &a) { return a.c; }
+__device__ __forceinline__ const Fp &dec_c(const Fp &a) { return a; }
+__device__ __forceinline__ const Fp &dec_c(const Fp2L &a) { return a.c; }
+
+// a value over the lanes of a point: G1 the lane's own, G2 combined with the partner's
+template <int G>
+__device__ __forceinline__ uint32_t dec_or(uint32_t v) {
+  return G == 2 ? (v | pair_swap(v)) : v;
+}
+template <int G>
+__device__ __forceinline__ uint32_t dec_swap(uint32_t v) {
+  return G == 2 ? pair_swap(v) : v;
+}
+template <int G>
+__device__ __forceinline__ bool dec_all(bool b) {
+  const uint32_t v = b ? 1u : 0u;
+  return (G == 2 ? (v & pair_swap(v)) : v) != 0;
+}
+
+// 48 big-endian bytes at s (4-byte aligned) -> integer limbs.  top = the three
+// flag bits of byte 0; nz = OR of the words (the flag bits left out when
+// `mask`, which also clears them in the value).
+__device__ __forceinline__ void dec_ld_be(Fp &r, uint32_t &top, uint32_t &nz, const uint32_t *s, bool mask) {
+  uint64_t l[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    uint32_t lo = __builtin_bswap32(s[11 - 2 * i]), hi = __builtin_bswap32(s[10 - 2 * i]);
+    if (i == 5) {
+      top = hi >> 29;
+      hi = mask ? (hi & 0x1fffffffu) : hi;
+    }
+    l[i] = ((uint64_t)hi << 32) | lo;
+  }
+  uint64_t o = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) o |= l[i];
+  nz = (uint32_t)o | (uint32_t)(o >> 32);
+  unpack384(r, l);
+}
+// a >= p for normalized integer limbs
+__device__ __forceinline__ bool dec_ge_p(const Fp &a) {
+  int32_t br = 0;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) br = ((int32_t)a.v[i] - (int32_t)P28[i] + br) >> 28;
+  return br == 0;
+}
+// a > (p - 1) / 2 for a canonical plain integer
+__device__ __forceinline__ bool dec_gt_half(const Fp &a) {
+  int32_t br = 0;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) br = ((int32_t)DEC_PM1H[i] - (int32_t)a.v[i] + br) >> 28;
+  return br != 0;
+}
+__device__ __forceinline__ void dec_mulk(Fp &r, const Fp &a, const uint32_t *c) {
+  Fp k;
+  fp_set(k, c);
+  fp_mul(r, a, k);
+}
+// the plain integer of an internal value (any lazy class), canonical
+__device__ __forceinline__ void dec_plain(Fp &r, const Fp &a) {
+  Fp one;
+  fp_zero(one);
+  one.v[0] = 1;
+  fp_mul(r, a, one);
+  fp_csub_p(r);
+}
+// a == b mod p; a normalized < 10p (class S or X), b in S
+__device__ __forceinline__ bool dec_eq(const Fp &a, const Fp &b) {
+  Fp d, c;
+  fp_sub<4>(d, a, b);  // a + 4p - b < 14p
+  fp_canon(c, d);
+  return fp_is_zero_exact(c);
+}
+// a + b == 0 mod p; a, b in S
+__device__ __forceinline__ bool dec_sum_is_zero(const Fp &a, const Fp &b) {
+  Fp d, c;
+  fp_add(d, a, b);
+  fp_canon(c, d);
+  return fp_is_zero_exact(c);
+}
+__device__ __forceinline__ void dec_sel(Fp &r, bool c, const Fp &a) {  // r = c ? a : r
+#pragma unroll
+  for (int i = 0; i < NL; ++i) r.v[i] = c ? a.v[i] : r.v[i];
+}
+
+// a^((p-3)/4): fixed 2-bit windows of a constant exponent (uniform control
+// flow), as fp_inv (ches_kernels.hpp).  Input any lazy value, output S.
+__device__ __forceinline__ void dec_pow_pm3d4(Fp &r, const Fp &a) {
+  Fp a1 = a, a2, a3, acc;
+  fp_norm(a1);
+  fp_sqr(a2, a1);
+  fp_mul(a3, a2, a1);
+  fp_one(acc);
+  for (int k = 189; k >= 0; --k) {  // 2-bit windows of (p - 3) / 4 (379 bits), from the top
+    if (k != 189) {
+      fp_sqr(acc, acc);
+      fp_sqr(acc, acc);
+    }
+    const uint32_t w = (uint32_t)(PM3D4[k >> 5] >> ((k & 31) * 2)) & 3u;
+    if (w) {
+      const uint32_t m1 = 0u - (uint32_t)(w == 1), m2 = 0u - (uint32_t)(w == 2), m3 = 0u - (uint32_t)(w == 3);
+      Fp t;
+#pragma unroll
+      for (int i = 0; i < NL; ++i) t.v[i] = (a1.v[i] & m1) | (a2.v[i] & m2) | (a3.v[i] & m3);
+      fp_mul(acc, acc, t);
+    }
+  }
+  r = acc;
+}
+
+// a candidate root of a (in S); the caller verifies y^2 == a
+__device__ __forceinline__ void dec_sqrt(Fp &y, const Fp &a) {
+  Fp r;
+  dec_pow_pm3d4(r, a);
+  fp_mul(y, r, a);
+}
+// Fp2 through the norm: with n = sqrt(a0^2 + a1^2), t = (a0 + n) / 2 (or
+// (a0 - n) / 2 when that is zero), r = t^((p-3)/4), c = r t, d = a1 r / 2:
+//   c^2 == t   ->  y = c + d i        (r = 1 / c)
+//   c^2 == -t  ->  y = -d + c i       (r = -1 / c; the other of the two t has the root)
+// Every value is formed on both lanes; each keeps its own component.  A
+// non-square a gives a y that fails the caller's y^2 == a.
+__device__ __forceinline__ void dec_sqrt(Fp2L &y, const Fp2L &a) {
+  const bool odd = pair_odd();
+  Fp par, a0, a1, n, s, t1, t2, r, c, d, c2;
+  pair_swap(par, a.c);
+  pair_sel(a0, odd, par, a.c);
+  pair_sel(a1, odd, a.c, par);
+  fp_sqr(n, a0);
+  fp_sqr(s, a1);
+  fp_add(n, n, s);  // < 4p lazy
+  dec_pow_pm3d4(r, n);
+  fp_norm(n);
+  fp_mul(s, r, n);  // sqrt of the norm, S
+  fp_add(t1, a0, s);
+  fp_sub<4>(t2, a0, s);
+  dec_mulk(t1, t1, DEC_HALF);
+  dec_mulk(t2, t2, DEC_HALF);
+  dec_sel(t1, fp_is_zero_lt2p(t1), t2);
+  dec_pow_pm3d4(r, t1);
+  fp_mul(c, r, t1);
+  fp_mul(d, a1, r);
+  dec_mulk(d, d, DEC_HALF);
+  fp_sqr(c2, c);
+  const bool good = dec_eq(c2, t1);
+  Fp nd;
+  fp_neg<4>(nd, d);
+  fp_nred(nd);
+  pair_sel(y.c, odd, d, c);     // good: even c, odd d
+  pair_sel(nd, odd, c, nd);     // else: even -d, odd c
+  dec_sel(y.c, !good, nd);
+}
+
+// the 0x20 flag of y (internal form): y > (p - 1) / 2, for Fp2 decided by the
+// imaginary part unless it is zero (ref sgn0_pty_mont_384x >> 1)
+__device__ __forceinline__ bool dec_sign(const Fp &y) {
+  Fp v;
+  dec_plain(v, y);
+  return dec_gt_half(v);
+}
+__device__ __forceinline__ bool dec_sign(const Fp2L &y) {
+  Fp v;
+  dec_plain(v, y.c);
+  const uint32_t own = (dec_gt_half(v) ? 1u : 0u) | (fp_is_zero_exact(v) ? 2u : 0u);
+  const uint32_t par = pair_swap(own);
+  const uint32_t im = pair_odd() ? own : par, re = pair_odd() ? par : own;
+  return ((im & 2u) ? (re & 1u) : (im & 1u)) != 0;
+}
+
+// lane (pair) t < n: entry t of src -> out[t], status[t]
+template <int G, bool SER>
+static __global__ void __launch_bounds__(128)
+    k_decode(const uint8_t *__restrict__ src, size_t n, uint64_t *__restrict__ out, uint8_t *__restrict__ status) {
+  typedef typename DecLane<G>::LF LF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= n) return;  // whole pairs only
+  // the imaginary part comes first and carries the flags
+  const bool lead = G == 1 || comp == 1;
+  const uint32_t *e = reinterpret_cast<const uint32_t *>(src + t * (SER ? 96 : 48) * G) + (lead ? 0 : 12);
+  Fp xi;
+  uint32_t top, nzo;
+  dec_ld_be(xi, top, nzo, e, lead);
+  // (the swap outside the lane-dependent choice: a DPP move under a divergent
+  // branch reads zero from the lanes the branch switched off)
+  const uint32_t ptop = dec_swap<G>(top);
+  const uint32_t flags = lead ? top : ptop;
+  const bool fc = (flags & 4u) != 0, finf = (flags & 2u) != 0, fsgn = (flags & 1u) != 0;
+  const bool x_zero = dec_or<G>(nzo) == 0;
+  const bool x_bad = dec_or<G>(dec_ge_p(xi) ? 1u : 0u) != 0;
+  LF x, a, y;
+  dec_mulk(dec_c(x), xi, DEC_R2);  // S
+  {
+    LF t2;
+    Fp four;
+    f_sqr(t2, x);
+    f_mul(a, t2, x);
+    fp_set(four, DEC_FOUR);
+    fp_add(dec_c(a), dec_c(a), four);
+    fp_nred(dec_c(a));  // a = x^3 + b, S
+  }
+  bool root_ok = false;
+  f_zero(y);
+  if (!SER || __builtin_amdgcn_ballot_w64(fc) != 0) {
+    LF y2;
+    dec_sqrt(y, a);
+    f_sqr(y2, y);
+    root_ok = dec_all<G>(dec_eq(dec_c(y2), dec_c(a)));
+    const bool neg = dec_sign(y) != fsgn;
+    fp_cneg4(dec_c(y), dec_c(y), neg);  // < 4p lazy
+  }
+  uint32_t st;
+  bool inf = false;
+  if (SER && flags == 0) {
+    Fp yi;
+    uint32_t ytop, ynz;
+    dec_ld_be(yi, ytop, ynz, e + 12 * G, false);
+    const bool y_bad = dec_or<G>(dec_ge_p(yi) ? 1u : 0u) != 0;
+    LF ys, y2;
+    dec_mulk(dec_c(ys), yi, DEC_R2);
+    f_sqr(y2, ys);
+    const bool on_curve = dec_all<G>(dec_eq(dec_c(y2), dec_c(a)));
+    st = (x_bad || y_bad) ? 1u : !on_curve ? 2u : (G == 1 && x_zero) ? 3u : 0u;
+    y = ys;
+  } else if (fc) {
+    if (finf) {
+      inf = !fsgn && x_zero;
+      st = inf ? 0u : 1u;
+    } else {
+      st = x_bad ? 1u : !root_ok ? 2u : (G == 1 && x_zero) ? 3u : 0u;
+    }
+  } else if (SER && finf) {
+    Fp yi;
+    uint32_t ytop, ynz;
+    dec_ld_be(yi, ytop, ynz, e + 12 * G, false);
+    inf = !fsgn && x_zero && dec_or<G>(ynz) == 0;
+    st = inf ? 0u : 1u;
+  } else {
+    st = 1u;
+  }
+  Fp xo, yo, zero;
+  dec_mulk(xo, dec_c(x), FROMINT28);
+  dec_mulk(yo, dec_c(y), FROMINT28);
+  fp_csub_p(xo);
+  fp_csub_p(yo);
+  fp_zero(zero);
+  dec_sel(xo, st != 0 || inf, zero);
+  dec_sel(yo, st != 0 || inf, zero);
+  uint64_t *o = out + t * 12 * G;
+  pack384(o + 6 * comp, xo);
+  pack384(o + 6 * G + 6 * comp, yo);
+  if (comp == 0) status[t] = (uint8_t)st;
+}
+
+// r = [k] p for the constant k = hi 2^64 + lo of `bits` bits (top bit set), p
+// affine and not infinity; r enters as p
+template <class F>
+__device__ __forceinline__ void dec_times(Xyzz<F> &r, const Aff<F> &p, uint64_t hi, uint64_t lo, int bits) {
+  for (int b = bits - 2; b >= 0; --b) {
+    Xyzz<F> tmp = r;
+    xyzz_dbl(r, tmp);
+    if (((b >= 64 ? hi >> (b - 64) : lo >> b) & 1) != 0) xyzz_madd(r, p, false);  // uniform: k is a constant
+  }
+}
+constexpr unsigned __int128 DEC_ZZ = (unsigned __int128)DEC_Z_ABS * DEC_Z_ABS;  // z^2, 128 bits
+constexpr uint64_t DEC_ZZ_HI = (uint64_t)(DEC_ZZ >> 64), DEC_ZZ_LO = (uint64_t)DEC_ZZ;
+static_assert((DEC_ZZ_HI >> 63) == 1 && (DEC_Z_ABS >> 63) == 1, "top bits");
+
+// lane (pair) t < n: a status-0 point outside the prime-order subgroup gets
+// status 3 and the all-zero output; everything else stays as it is
+template <int G>
+static __global__ void __launch_bounds__(128, 2) k_decode_group(uint64_t *out, uint8_t *status, size_t n) {
+  typedef typename DecLane<G>::LF LF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= n) return;  // whole pairs only
+  uint64_t *o = out + t * 12 * G;
+  Aff<LF> p;
+  fp_from_blst(dec_c(p.x), o + 6 * comp);
+  fp_from_blst(dec_c(p.y), o + 6 * G + 6 * comp);
+  const bool zx = f_is_zero_exact(p.x), zy = f_is_zero_exact(p.y);
+  const bool skip = status[t] != 0 || (zx && zy);
+  Xyzz<LF> q;
+  xyzz_from_aff(q, p, false);
+  LF ex, ey;  // [k]P must equal (ex, -ey), affine
+  if constexpr (G == 1) {
+    dec_times(q, p, DEC_ZZ_HI, DEC_ZZ_LO, 128);
+    ey = p.y;
+    dec_mulk(ex, p.x, DEC_BETA);
+  } else {
+    dec_times(q, p, 0, DEC_Z_ABS, 64);
+    // psi: conjugate, then the constants (cx = cx1 i)
+    const bool odd = pair_odd();
+    LF cx, cy, t1, t2;
+    fp_zero(cx.c);
+    Fp k;
+    fp_set(k, DEC_PSI_CX1);
+    dec_sel(cx.c, odd, k);
+    fp_set(cy.c, DEC_PSI_CY0);
+    fp_set(k, DEC_PSI_CY1);
+    dec_sel(cy.c, odd, k);
+    fp_cneg4(t1.c, p.x.c, odd);
+    fp_cneg4(t2.c, p.y.c, odd);
+    f_mul(ex, t1, cx);
+    f_mul(ey, t2, cy);
+  }
+  // q == (ex, -ey):  X == ex ZZ,  Y + ey ZZZ == 0
+  LF u, v;
+  f_mul_bs(u, ex, q.zz);
+  f_mul_bs(v, ey, q.zzz);
+  const bool eq_x = dec_eq(dec_c(q.x), dec_c(u)), eq_y = dec_sum_is_zero(dec_c(q.y), dec_c(v));
+  bool ok = eq_x & eq_y;
+  const bool q_inf = xyzz_is_inf(q);
+  ok = dec_all<G>(ok) && !q_inf;
+  if (!skip && !ok) {
+    Fp zero;
+    fp_zero(zero);
+    pack384(o + 6 * comp, zero);
+    pack384(o + 6 * G + 6 * comp, zero);
+    if (comp == 0) status[t] = 3;
+  }
+}
+
+template <int G>
+Decode<G>::Decode(int device) : dev_(device) {
+  DeviceGuard g(dev_);
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
+  }
+  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
+}
+
+template <int G>
+Decode<G>::~Decode() {
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(dev_);
+  // queued work may still read the staging and status buffers
+  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
+  if (h2d_) (void)hipStreamSynchronize(h2d_);
+  if (d2h_) (void)hipStreamSynchronize(d2h_);
+  for (int i = 0; i < 2; ++i) {
+    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
+    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
+    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
+    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
+    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
+    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
+    if (pin_st_[i]) (void)hipHostFree(pin_st_[i]);
+  }
+  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
+  if (h2d_) (void)hipStreamDestroy(h2d_);
+  if (d2h_) (void)hipStreamDestroy(d2h_);
+  if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+template <int G>
+void Decode<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
+  if (bytes <= have) return;
+  for (int i = 0; i < 2; ++i) {
+    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
+    slots[i] = nullptr;
+  }
+  have = 0;
+  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
+  have = bytes;
+}
+
+// one chunk, device to device
+template <int G>
+void Decode<G>::kernels(hipStream_t s, const void *d_src, void *d_dst, uint8_t *d_status, size_t n, bool serialized,
+                        bool check_group) {
+  const unsigned B = 128;
+  const dim3 grid(nblk(n * G, B));
+  if (serialized)
+    hipLaunchKernelGGL((k_decode<G, true>), grid, dim3(B), 0, s, static_cast<const uint8_t *>(d_src), n,
+                       static_cast<uint64_t *>(d_dst), d_status);
+  else
+    hipLaunchKernelGGL((k_decode<G, false>), grid, dim3(B), 0, s, static_cast<const uint8_t *>(d_src), n,
+                       static_cast<uint64_t *>(d_dst), d_status);
+  MSM_HIP_CHECK(hipGetLastError());
+  if (check_group) {
+    hipLaunchKernelGGL(k_decode_group<G>, grid, dim3(B), 0, s, static_cast<uint64_t *>(d_dst), d_status, n);
+    MSM_HIP_CHECK(hipGetLastError());
+  }
+}
+
+template <int G>
+void Decode<G>::run(hipStream_t cs, const void *src, void *dst, uint8_t *status, size_t n, bool serialized,
+                    bool check_group, bool src_dev, bool dst_dev) {
+  if (!n) return;
+  DeviceGuard g(dev_);
+  const size_t ENC = serialized ? 2 * COMP : COMP;
+  const size_t C = std::min(n, dec_chunk());
+  const bool out_host = !dst_dev || status;  // something comes back per chunk
+  dst_[0].ensure(C);
+  dst_[1].ensure(C);
+  if (!src_dev) {
+    ensure_pinned(pin_in_, pin_in_bytes_, C * ENC);
+    din_[0].ensure(C * ENC);
+    din_[1].ensure(C * ENC);
+  }
+  if (!dst_dev) {
+    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
+    dout_[0].ensure(C * AFF);
+    dout_[1].ensure(C * AFF);
+  }
+  if (status) ensure_pinned(pin_st_, pin_st_bytes_, C);
+  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the status buffers of the previous call
+  struct Pending {
+    int slot;
+    size_t off, cnt;
+  } prev{0, 0, 0};
+  auto drain = [&](const Pending &p) {
+    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
+    if (!dst_dev) memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
+    if (status) memcpy(status + p.off, pin_st_[p.slot], p.cnt);
+  };
+  size_t k = 0;
+  for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
+    const size_t cnt = std::min(C, n - c0);
+    const int slot = (int)(k & 1);
+    const void *d_src;
+    void *d_dst;
+    if (!src_dev) {
+      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
+      memcpy(pin_in_[slot], static_cast<const uint8_t *>(src) + c0 * ENC, cnt * ENC);
+      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
+      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], cnt * ENC, hipMemcpyHostToDevice, h2d_));
+      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
+      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
+      d_src = din_[slot].p;
+    } else {
+      d_src = static_cast<const uint8_t *>(src) + c0 * ENC;
+    }
+    if (out_host) MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_ / dst_[slot]
+    d_dst = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * AFF) : dout_[slot].p;
+    kernels(cs, d_src, d_dst, dst_[slot].as<uint8_t>(), cnt, serialized, check_group);
+    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    if (out_host) {
+      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
+      if (!dst_dev)
+        MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * AFF, hipMemcpyDeviceToHost, d2h_));
+      if (status) MSM_HIP_CHECK(hipMemcpyAsync(pin_st_[slot], dst_[slot].p, cnt, hipMemcpyDeviceToHost, d2h_));
+      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
+      if (k) drain(prev);  // chunk k - 1, while chunk k runs
+      prev = Pending{slot, c0, cnt};
+    }
+  }
+  if (out_host) drain(prev);
+  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+}
+
+template class Decode<MSM_GROUP>;
+
+}  // namespace msm
