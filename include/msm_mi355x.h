@@ -446,6 +446,39 @@ int msm_points_decode(int group, int device, void *dst_affine, uint8_t *status, 
 int msm_ctx_set_points_encoded(msm_ctx *ctx, const void *src, size_t npoints, int encoding, int flags,
                                int src_on_device, size_t *first_bad, void *hip_stream);
 
+/* ---- bulk scalar multiplication (replaces a loop over the reference's one-point
+ * blst_p{1,2}_mult / blst_p{1,2}_unchecked_mult: ref src/e1.c:505-533, src/e2.c,
+ * src/ec_mult.h) ----
+ * dst[i] = [k_i] P_i as a canonical affine point in blst Montgomery layout (infinity:
+ * all zero), for i < npoints.  P_i: affine point i of points_affine (all zero:
+ * infinity, which gives infinity); with MSM_MULT_ONE_POINT points_affine holds ONE
+ * point, used for every scalar (fixed base).  k_i: the integer in the low nbits bits
+ * of the little-endian scalar at scalars + i scalar_stride, 0 <= nbits <= 256,
+ * (nbits + 7) / 8 <= scalar_stride <= 2^20.  Bits at and above nbits in the last byte are
+ * ignored (masked), and no byte beyond (nbits + 7) / 8 of a scalar is read.
+ * nbits == 0: every output is infinity.
+ * The result is the exact [k_i] P_i for every point of the curve, in the prime-order
+ * subgroup or not: the contract of blst_p{1,2}_unchecked_mult, which coincides with
+ * blst_p{1,2}_mult on subgroup points.  (No endomorphism split of the scalar is used;
+ * it is only valid inside the subgroup.)
+ * points and scalars are both in host memory or both in device memory
+ * (src_on_device; device points 8-byte aligned, scalars unaligned); dst in host or
+ * device memory (8-byte aligned), on HIP device `device`.
+ * npoints == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: a NULL
+ * pointer with npoints > 0, group other than 1 or 2, nbits > 256, a scalar_stride
+ * shorter than (nbits + 7) / 8, unknown flag bits, host sources overlapping a host
+ * dst.  MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP failure; a host dst is then
+ * zero-filled.  Streams as msm_points_to_affine.  On the GPU: csrc/points_mult.hip, a
+ * ladder over signed 4-bit windows on a per-point table of 8 affine rows kept in
+ * device memory for one chunk of at most 2^18 points (MSM_POINTS_MULT_CHUNK=<points>
+ * overrides, read at each call), host memory through two pinned staging buffers per
+ * direction.  Thread-safe per call (an engine pool keyed by (device, group), counted
+ * by msm_engine_cache_stats(), freed by msm_release_engine_cache()). */
+#define MSM_MULT_ONE_POINT 1 /* points_affine holds ONE point, used for every scalar (fixed base) */
+int msm_points_mult(int group, int device, void *dst_affine, const void *points_affine, const byte *scalars,
+                    size_t npoints, size_t nbits, size_t scalar_stride, int flags, int src_on_device,
+                    int dst_on_device, void *hip_stream);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

@@ -14,6 +14,8 @@ Mirrors:
   ps_to_affine                                        blst_p{1,2}s_to_affine (ref multi_scalar.c:17-62), bulk, on the GPU
   ps_decode, MSMContext.set_points_encoded            blst_p{1,2}_uncompress / _deserialize / _affine_in_g{1,2}
                                                       (ref e1.c:236-351, e2.c:279-410), bulk, on the GPU
+  ps_mult                                             out[i] = [k_i]P_i: a loop over blst_p{1,2}_mult / _unchecked_mult
+                                                      (ref e1.c:505-533, ec_mult.h), bulk, on the GPU
 """
 import ctypes
 
@@ -23,12 +25,13 @@ from .ches import CHESContext
 from .wbits import WbitsContext
 
 __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext", "p1s_mult_pippenger", "p2s_mult_pippenger", "ps_add", "fixed_points", "gen_scalars",
-           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "device_count", "lib"]
+           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "ps_mult", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
 JAC_BYTES = {1: 144, 2: 288}
 ENC_COMPRESSED, ENC_SERIALIZED = 0, 1  # MSM_ENC_*: 48 G / 96 G bytes per entry
 DECODE_CHECK_GROUP = 1                 # MSM_DECODE_CHECK_GROUP
+MULT_ONE_POINT = 1                     # MSM_MULT_ONE_POINT
 
 
 def device_count():
@@ -143,6 +146,47 @@ def ps_decode(group, data, n, *, compressed=True, check_group=True, src_on_devic
     check(lib().msm_points_decode(group, device, out, status, None, src, n, enc, flags, int(bool(src_on_device)), 0,
                                   stream))
     return bytes(out), bytes(status)
+
+
+def ps_mult(group, points, scalars, n, *, nbits=255, stride=32, one_point=False, src_on_device=False, dst=None,
+            device=0, stream=None):
+    """out[i] = [k_i] P_i for i < n as affine bytes (msm_points_mult; infinity is the
+    all-zero point).  points: n affine points, or ONE with one_point (fixed base).
+    k_i: the low nbits bits of the little-endian scalar at scalars[i * stride:]; bits
+    above nbits in the last byte are ignored.  The result is exact for every point of
+    the curve, subgroup or not.  Host sources are bytes-like objects, device sources
+    (src_on_device, both) device pointers.  With dst=<device pointer> the points are
+    written there, ordered on `stream`, and None is returned."""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if not 0 <= nbits <= 256:
+        raise ValueError("nbits must be in [0, 256]")
+    nb = (nbits + 7) // 8
+    if stride < nb:
+        raise ValueError(f"stride {stride} shorter than the {nb} bytes of a {nbits}-bit scalar")
+    if src_on_device:
+        pts, sc = points, scalars
+    else:
+        pts, sc = _buf(points), _buf(scalars)
+        have = len(pts) if hasattr(pts, "__len__") else ctypes.sizeof(pts)
+        need = POINT_BYTES[group] * (min(n, 1) if one_point else n)
+        if have < need:
+            raise ValueError(f"{have} bytes of points given, {need} needed")
+        have = len(sc) if hasattr(sc, "__len__") else ctypes.sizeof(sc)
+        need = (n - 1) * stride + nb if n else 0
+        if have < need:
+            raise ValueError(f"{have} bytes of scalars given, {need} needed")
+    flags = MULT_ONE_POINT if one_point else 0
+    if dst is not None:
+        check(lib().msm_points_mult(group, device, dst, pts, sc, n, nbits, stride, flags, int(bool(src_on_device)), 1,
+                                    stream))
+        return None
+    out = (ctypes.c_uint8 * (POINT_BYTES[group] * n))()
+    check(lib().msm_points_mult(group, device, out, pts, sc, n, nbits, stride, flags, int(bool(src_on_device)), 0,
+                                stream))
+    return bytes(out)
 
 
 def to_affine_levels(n):

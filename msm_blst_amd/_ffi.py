@@ -129,6 +129,7 @@ def lib():
     L.msm_to_affine_levels.argtypes = [sz]
     L.msm_points_decode.argtypes = [i32, i32, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]
     L.msm_ctx_set_points_encoded.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp]
+    L.msm_points_mult.argtypes = [i32, i32, vp, vp, vp, sz, sz, sz, i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -20,6 +20,7 @@
 #include "decode.hpp"
 #include "engine.hpp"
 #include "multi.hpp"
+#include "points_mult.hpp"
 #include "pool.hpp"
 #include "ptr_walk.hpp"
 #include "table_registry.hpp"
@@ -405,6 +406,56 @@ int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t
   }
 }
 
+// ---- bulk scalar multiplication (a loop over ref e1.c:505-533 blst_p1_mult, e2.c, ec_mult.h) ----
+// cs orders the kernels: the caller's stream when a side is device memory, else
+// the leased engine's own.
+template <int G>
+void points_mult(int dev, void *dst, const void *points, const uint8_t *scalars, size_t n, int nbits, size_t stride,
+                 bool one_point, bool src_dev, bool dst_dev, hipStream_t user) {
+  DeviceGuard g(dev);
+  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+  if (nbits == 0) {  // every scalar is zero
+    if (dst_dev) MSM_HIP_CHECK(hipMemsetAsync(dst, 0, n * 96 * G, user));
+    else memset(dst, 0, n * 96 * G);
+    if (dst_dev && !user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+    return;
+  }
+  auto eng = EnginePool<PointsMult<G>>::get().lease(dev, G, [&] { return std::make_unique<PointsMult<G>>(dev); });
+  const bool on_user = src_dev || dst_dev;
+  hipStream_t cs = on_user ? user : eng->stream();
+  (*eng)->run(cs, points, scalars, dst, n, nbits, stride, one_point, src_dev, dst_dev);
+  // the legacy default stream gives the caller nothing to wait on: finish here
+  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+int points_mult_checked(int group, int dev, void *dst, const void *points, const byte *scalars, size_t n, size_t nbits,
+                        size_t stride, int flags, bool src_dev, bool dst_dev, hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (nbits > 256) return fail(MSM_E_ARG, "nbits must be at most 256");
+  if (stride < (nbits + 7) / 8) return fail(MSM_E_ARG, "scalar_stride shorter than (nbits + 7) / 8");
+  if (flags & ~MSM_MULT_ONE_POINT) return fail(MSM_E_ARG, "unknown flag bits");
+  if (n == 0) return MSM_OK;  // nothing touched
+  if (!dst || !points || !scalars) return fail(MSM_E_ARG, "null dst / points / scalars");
+  if (n > ((size_t)1 << 40) || stride > ((size_t)1 << 20)) return fail(MSM_E_ARG, "npoints / scalar_stride out of range");
+  const bool one = (flags & MSM_MULT_ONE_POINT) != 0;
+  const size_t aff = (size_t)96 * group, pbytes = (one ? 1 : n) * aff, sbytes = (n - 1) * stride + (nbits + 7) / 8;
+  if (!src_dev && !dst_dev && (ranges_overlap(points, pbytes, dst, n * aff) || ranges_overlap(scalars, sbytes, dst, n * aff)))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (src_dev && ((uintptr_t)points & 7) != 0) return fail(MSM_E_ARG, "device points not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    if (group == 1) points_mult<1>(dev, dst, points, scalars, n, (int)nbits, stride, one, src_dev, dst_dev, user);
+    else points_mult<2>(dev, dst, points, scalars, n, (int)nbits, stride, one, src_dev, dst_dev, user);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (!dst_dev) memset(dst, 0, n * aff);  // never half written
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   size_t w = 0;
   while (n >>= 1) ++w;
@@ -767,6 +818,13 @@ int msm_points_decode(int group, int device, void *dst, uint8_t *status, size_t 
                       int encoding, int flags, int src_on_device, int dst_on_device, void *hip_stream) {
   return points_decode_checked(group, device, dst, status, nbad, src, npoints, encoding, flags, src_on_device != 0,
                                dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_points_mult(int group, int device, void *dst, const void *points, const byte *scalars, size_t npoints,
+                    size_t nbits, size_t scalar_stride, int flags, int src_on_device, int dst_on_device,
+                    void *hip_stream) {
+  return points_mult_checked(group, device, dst, points, scalars, npoints, nbits, scalar_stride, flags,
+                             src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
 }
 
 const char *msm_last_error(void) { return g_err.c_str(); }

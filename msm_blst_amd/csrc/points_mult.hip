@@ -1,0 +1,336 @@
+// points_mult.hip -- bulk scalar multiplication out[i] = [k_i] P_i on one MI355X
+// (replaces a loop over the reference's one-point blst_p{1,2}_mult: ref
+// src/e1.c:505-533, src/e2.c, src/ec_mult.h).
+//
+// A fixed-window ladder over signed 4-bit digits, the same for every lane:
+//   k_pm_table   point t -> its multiples 1P .. 8P: 1P as an affine row, 2P .. 8P
+//                as xyzz points by a chain of xyzz_madd (which takes the doubling
+//                branch for 2P and restarts from P after a multiple that is
+//                infinity, so points of small order need no care)
+//   (ta_tree)    the 7 xyzz multiples of every point -> affine rows, through the
+//                batch-inversion tree of to_affine.hip (TA_XYZZ_ROWS)
+//   k_pm_ladder  from the top window down: four doublings, then the row
+//                |digit| of the lane's own point added or subtracted
+//                (xyzz_madd).  Every lane runs the same windows and the same
+//                doublings; a zero digit or an all-zero row (infinity) is
+//                skipped under a predicate.  The rows are read from HBM by a
+//                lane-varying index (a register array indexed that way would
+//                be scratch), row m of point t at rows[(m - 1) np + t].
+//   (ta_tree)    the ladder's xyzz results -> blst affine output (TA_XYZZ_BLST)
+//
+// Digits (Booth): window w looks at bits 4w - 1 .. 4w + 3 of the scalar (bit -1
+// and bits >= nbits are zero), d = b[4w-1] + b[4w] + 2 b[4w+1] + 4 b[4w+2] - 8 b[4w+3]
+// in [-8, 8]; sum d_w 16^w = k over nbits / 4 + 1 windows, no carry chain, so a
+// lane reads two scalar bytes per window and the ladder can start at the top.
+//
+// The result is [k]P for every point of the curve, in the subgroup or not (the
+// contract of blst_p{1,2}_unchecked_mult): no endomorphism is used.
+//
+// G1 runs one lane per point, G2 one lane PAIR per point (Fp2L, fp2l.hpp).  Both
+// lanes of a pair hold the same digit and the same zero tests (f_is_zero_exact
+// combines the pair), so every branch is taken by whole pairs and a DPP swap
+// never reads a switched-off partner.
+//
+// Products per point as built at nbits = 255 (an fp_mul2 priced 1.5 Fp products,
+// an fp_mul4 2.5; tools/points_mult_timing.py): 64 windows, 252 doublings of 8.5
+// and 60 mixed additions of 9.5 (a digit is zero with probability 1/16) = 2712;
+// table 2 + 12.5 + 6 x 9.5 = 71.5, its rows 7 x 8.6 = 60, the output 9.7:
+// G1 2853; G2, both lanes, 7814.  One-point mode drops the table and the rows.
+#include "points_mult.hpp"
+
+#include <cstring>
+
+#include "pair_kernels.hpp"
+#include "to_affine.hpp"
+
+#ifndef MSM_GROUP
+#error "define MSM_GROUP (1 or 2)"
+#endif
+
+namespace msm {
+
+template <int G>
+struct PmLane;
+template <>
+struct PmLane<1> {
+  typedef Fp LF;
+};
+template <>
+struct PmLane<2> {
+  typedef Fp2L LF;
+};
+
+// stored elements (internal limbs, 56 B per component, 8-B aligned)
+__device__ __forceinline__ void pm_ld(Fp &r, const Fp *p, int) {
+  const uint2 *s = reinterpret_cast<const uint2 *>(p);
+#pragma unroll
+  for (int i = 0; i < NL / 2; ++i) {
+    const uint2 v = s[i];
+    r.v[2 * i] = v.x;
+    r.v[2 * i + 1] = v.y;
+  }
+}
+__device__ __forceinline__ void pm_ld(Fp2L &r, const Fp2 *p, int comp) { ld_comp(r.c, p, comp); }
+__device__ __forceinline__ void pm_st(Fp *p, const Fp &a, int) {
+  uint2 *d = reinterpret_cast<uint2 *>(p);
+#pragma unroll
+  for (int i = 0; i < NL / 2; ++i) d[i] = make_uint2(a.v[2 * i], a.v[2 * i + 1]);
+}
+__device__ __forceinline__ void pm_st(Fp2 *p, const Fp2L &a, int comp) { st_comp(p, a.c, comp); }
+template <class LF, class SF>
+__device__ __forceinline__ void pm_st_xyzz(Xyzz<SF> *p, const Xyzz<LF> &a, int comp) {
+  pm_st(&p->x, a.x, comp);
+  pm_st(&p->y, a.y, comp);
+  pm_st(&p->zzz, a.zzz, comp);
+  pm_st(&p->zz, a.zz, comp);
+}
+__device__ __forceinline__ Fp &pm_c(Fp &a) { return a; }
+__device__ __forceinline__ Fp &pm_c(Fp2L &a) { return a.c; }
+
+// the signed digit of window w (see the head of this file); k: the lane's
+// scalar, only bytes below (nbits + 7) / 8 are read.  w is uniform.
+__device__ __forceinline__ int pm_digit(const uint8_t *k, int w, int nbits) {
+  const int lo = 4 * w - 1;  // the lowest of the five bits
+  const int nb = (nbits + 7) >> 3;
+  uint32_t v = 0;
+  if (w == 0) {
+    if (nb > 0) v = (uint32_t)k[0] << 1;
+  } else {
+    const int q = lo >> 3;
+    if (q < nb) v = k[q];
+    if (q + 1 < nb) v |= (uint32_t)k[q + 1] << 8;
+    v >>= (lo & 7);
+  }
+  v &= 31u;
+  const int valid = nbits - lo;  // bits of the five below nbits
+  if (valid < 5) v &= valid > 0 ? (1u << valid) - 1u : 0u;
+  return (int)(v & 1u) + (int)((v >> 1) & 7u) - 8 * (int)(v >> 4);
+}
+
+// lane (pair) t < n: rows[t] = P_t (canonical internal limbs; infinity all zero),
+// xz[(m - 2) n + t] = [m] P_t for m = 2 .. 8
+template <int G>
+static __global__ void __launch_bounds__(128)
+    k_pm_table(const uint64_t *__restrict__ pts, size_t n, Aff<typename FieldOf<G>::F> *__restrict__ rows,
+               Xyzz<typename FieldOf<G>::F> *__restrict__ xz) {
+  typedef typename PmLane<G>::LF LF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= n) return;  // whole pairs only
+  const uint64_t *src = pts + t * 12 * G;
+  Aff<LF> p;
+  fp_from_blst(pm_c(p.x), src + 6 * comp);
+  fp_from_blst(pm_c(p.y), src + 6 * G + 6 * comp);
+  const bool zx = f_is_zero_exact(p.x), zy = f_is_zero_exact(p.y);
+  const bool inf = zx & zy;  // uniform over a pair
+  pm_st(&rows[t].x, p.x, comp);
+  pm_st(&rows[t].y, p.y, comp);
+  Xyzz<LF> q;
+  if (inf) xyzz_set_inf(q);
+  else xyzz_from_aff(q, p, false);
+#pragma unroll 1
+  for (int m = 2; m <= PM_ROWS; ++m) {
+    if (!inf) xyzz_madd(q, p, false);
+    pm_st_xyzz(&xz[(size_t)(m - 2) * n + t], q, comp);
+  }
+}
+
+// lane (pair) t < n: out[t] = [k_t] P, P = point t (np == n) or point 0 (np == 1) of the rows
+template <int G>
+static __global__ void __launch_bounds__(128, 2)
+    k_pm_ladder(const Aff<typename FieldOf<G>::F> *__restrict__ rows, size_t np, const uint8_t *__restrict__ sc,
+                size_t stride, int nbits, Xyzz<typename FieldOf<G>::F> *__restrict__ out, size_t n) {
+  typedef typename PmLane<G>::LF LF;
+  const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int comp = G == 2 ? (int)(tt & 1) : 0;
+  const size_t t = G == 2 ? tt >> 1 : tt;
+  if (t >= n) return;  // whole pairs only
+  const uint8_t *k = sc + t * stride;
+  const Aff<typename FieldOf<G>::F> *mine = rows + (np == 1 ? 0 : t);
+  const int nw = nbits / 4 + 1;
+  Xyzz<LF> acc;
+  xyzz_set_inf(acc);
+#pragma unroll 1
+  for (int w = nw - 1; w >= 0; --w) {
+    const int d = pm_digit(k, w, nbits);
+    const uint32_t m = (uint32_t)(d < 0 ? -d : d);
+    // the row is asked for before the doublings, which hide its latency
+    Aff<LF> row;
+    f_zero(row.x);
+    f_zero(row.y);
+    if (m) {
+      const Aff<typename FieldOf<G>::F> *r = mine + (size_t)(m - 1) * np;
+      pm_ld(row.x, &r->x, comp);
+      pm_ld(row.y, &r->y, comp);
+    }
+    if (w != nw - 1) {
+#pragma unroll 1
+      for (int j = 0; j < 4; ++j) {
+        Xyzz<LF> tmp = acc;
+        xyzz_dbl(acc, tmp);
+      }
+    }
+    const bool zx = f_is_zero_exact(row.x), zy = f_is_zero_exact(row.y);
+    if (!(zx & zy)) xyzz_madd(acc, row, d < 0);  // (a zero digit left the row zero)
+  }
+  pm_st_xyzz(&out[t], acc, comp);
+}
+
+template <int G>
+PointsMult<G>::PointsMult(int device) : dev_(device) {
+  DeviceGuard g(dev_);
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
+  }
+  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
+}
+
+template <int G>
+PointsMult<G>::~PointsMult() {
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(dev_);
+  // queued work may still read the staging, table and level buffers
+  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
+  if (h2d_) (void)hipStreamSynchronize(h2d_);
+  if (d2h_) (void)hipStreamSynchronize(d2h_);
+  for (int i = 0; i < 2; ++i) {
+    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
+    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
+    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
+    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
+    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
+    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
+  }
+  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
+  if (h2d_) (void)hipStreamDestroy(h2d_);
+  if (d2h_) (void)hipStreamDestroy(d2h_);
+  if (prev >= 0) (void)hipSetDevice(prev);
+}
+
+template <int G>
+void PointsMult<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
+  if (bytes <= have) return;
+  for (int i = 0; i < 2; ++i) {
+    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
+    slots[i] = nullptr;
+  }
+  have = 0;
+  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
+  have = bytes;
+}
+
+template <int G>
+void PointsMult<G>::table(hipStream_t s, const void *d_points, size_t np) {
+  typedef typename FieldOf<G>::F SF;
+  static_assert(sizeof(Aff<SF>) == ROW && sizeof(Xyzz<SF>) == XYZZ && sizeof(SF) == ELEM, "stored sizes");
+  const size_t nx = (size_t)(PM_ROWS - 1) * np;
+  if (PM_ROWS * np * ROW > rows_.bytes || nx * XYZZ > xz_.bytes) throw std::runtime_error("points_mult: table buffer too small");
+  const unsigned B = 128;
+  hipLaunchKernelGGL(k_pm_table<G>, dim3(nblk(np * G, B)), dim3(B), 0, s, static_cast<const uint64_t *>(d_points), np,
+                     rows_.as<Aff<SF>>(), xz_.as<Xyzz<SF>>());
+  MSM_HIP_CHECK(hipGetLastError());
+  ta_tree<G>(s, lv_.p, lv_.bytes, TA_XYZZ_ROWS, xz_.p, rows_.as<Aff<SF>>() + np, nx);
+}
+
+template <int G>
+void PointsMult<G>::ladder(hipStream_t s, size_t np, const uint8_t *d_scalars, void *d_dst, size_t n, int nbits,
+                           size_t stride) {
+  typedef typename FieldOf<G>::F SF;
+  if (n * XYZZ > xz_.bytes) throw std::runtime_error("points_mult: result buffer too small");
+  const unsigned B = 128;
+  hipLaunchKernelGGL(k_pm_ladder<G>, dim3(nblk(n * G, B)), dim3(B), 0, s, (const Aff<SF> *)rows_.as<Aff<SF>>(), np,
+                     d_scalars, stride, nbits, xz_.as<Xyzz<SF>>(), n);
+  MSM_HIP_CHECK(hipGetLastError());
+  ta_tree<G>(s, lv_.p, lv_.bytes, TA_XYZZ_BLST, xz_.p, d_dst, n);
+}
+
+template <int G>
+void PointsMult<G>::run(hipStream_t cs, const void *points, const uint8_t *scalars, void *dst, size_t n, int nbits,
+                        size_t stride, bool one_point, bool src_dev, bool dst_dev) {
+  if (!n) return;
+  if (nbits < 1 || nbits > 256 || stride < (size_t)(nbits + 7) / 8) throw std::runtime_error("points_mult: bad nbits / stride");
+  DeviceGuard g(dev_);
+  const size_t nb = (size_t)(nbits + 7) / 8;
+  const size_t C = std::min(n, pm_chunk());
+  const size_t T = one_point ? 1 : C;                // points of a table
+  const size_t PB = T * AFF;                         // their bytes in a staged slot; the scalars follow
+  const size_t IN = PB + C * nb;                     // (staged scalars are packed: nb bytes apart)
+  rows_.ensure(PM_ROWS * T * ROW);
+  xz_.ensure(std::max((size_t)(PM_ROWS - 1) * T, C) * XYZZ);
+  lv_.ensure(std::max(ta_level_elems((size_t)(PM_ROWS - 1) * T), ta_level_elems(C)) * ELEM);
+  if (!src_dev) {
+    ensure_pinned(pin_in_, pin_in_bytes_, IN);
+    din_[0].ensure(IN);
+    din_[1].ensure(IN);
+  }
+  if (!dst_dev) {
+    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
+    dout_[0].ensure(C * AFF);
+    dout_[1].ensure(C * AFF);
+  }
+  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the table and level buffers of the previous call
+  struct Pending {
+    int slot;
+    size_t off, cnt;
+  } prev{0, 0, 0};
+  auto drain = [&](const Pending &p) {
+    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
+    memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
+  };
+  size_t k = 0;
+  for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
+    const size_t cnt = std::min(C, n - c0);
+    const int slot = (int)(k & 1);
+    const size_t np = one_point ? 1 : cnt;
+    const uint8_t *d_pts, *d_sc;
+    size_t d_stride = stride;
+    void *d_dst;
+    if (!src_dev) {
+      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
+      uint8_t *w = static_cast<uint8_t *>(pin_in_[slot]);
+      memcpy(w, static_cast<const uint8_t *>(points) + (one_point ? 0 : c0 * AFF), np * AFF);
+      const uint8_t *sc = scalars + c0 * stride;
+      if (stride == nb) memcpy(w + PB, sc, cnt * nb);
+      else  // only the nb bytes of each scalar: nothing past the last one is read, and the slot stays small
+        for (size_t i = 0; i < cnt; ++i) memcpy(w + PB + i * nb, sc + i * stride, nb);
+      d_stride = nb;
+      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
+      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], PB + cnt * nb, hipMemcpyHostToDevice, h2d_));
+      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
+      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
+      d_pts = din_[slot].as<uint8_t>();
+      d_sc = d_pts + PB;
+    } else {
+      d_pts = static_cast<const uint8_t *>(points) + (one_point ? 0 : c0 * AFF);
+      d_sc = scalars + c0 * stride;
+    }
+    if (!dst_dev) {
+      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
+      d_dst = dout_[slot].p;
+    } else {
+      d_dst = static_cast<uint8_t *>(dst) + c0 * AFF;
+    }
+    if (!one_point || k == 0) table(cs, d_pts, np);  // one point: its rows serve every chunk
+    ladder(cs, np, d_sc, d_dst, cnt, nbits, d_stride);
+    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    if (!dst_dev) {
+      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
+      MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * AFF, hipMemcpyDeviceToHost, d2h_));
+      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
+      if (k) drain(prev);  // chunk k - 1, while chunk k runs
+      prev = Pending{slot, c0, cnt};
+    }
+  }
+  if (!dst_dev) drain(prev);
+  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+}
+
+template class PointsMult<MSM_GROUP>;
+
+}  // namespace msm

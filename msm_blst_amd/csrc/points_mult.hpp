@@ -1,0 +1,69 @@
+// points_mult.hpp -- bulk scalar multiplication out[i] = [k_i] P_i on the GPU
+// (replaces a loop over the reference's one-point blst_p{1,2}_mult /
+// _unchecked_mult: ref src/e1.c:505-533, src/e2.c, src/ec_mult.h; kernels and
+// orchestration in points_mult.hip).  This header is host-only.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "engine.hpp"
+
+namespace msm {
+
+constexpr size_t PM_CHUNK_DEFAULT = (size_t)1 << 18;
+constexpr int PM_ROWS = 8;  // 1P .. 8P: signed 4-bit windows
+
+// points per chunk: MSM_POINTS_MULT_CHUNK=<points> overrides the default, read at each call
+inline size_t pm_chunk() {
+  const char *e = getenv("MSM_POINTS_MULT_CHUNK");
+  if (e && *e) {
+    const long long v = atoll(e);
+    if (v > 0) return (size_t)v;
+  }
+  return PM_CHUNK_DEFAULT;
+}
+
+// One engine: the table of a chunk (xyzz multiples, then their affine rows),
+// the level buffer of the shared inversion tree (to_affine.hpp), and for host
+// memory two pinned + two device staging buffers per direction with their own
+// copy streams.  A staged input slot holds the points followed by the scalars,
+// packed (nbits + 7) / 8 bytes apart.
+template <int G>
+class PointsMult {
+ public:
+  static constexpr size_t AFF = 96 * G, ROW = 112 * G, XYZZ = 224 * G, ELEM = 56 * G;
+  explicit PointsMult(int device);
+  ~PointsMult();
+  PointsMult(const PointsMult &) = delete;
+  PointsMult &operator=(const PointsMult &) = delete;
+  // dst[i] = [k_i] P_i for i < n, k_i = the low nbits bits of the little-endian
+  // scalar at scalars + i stride (0 < nbits <= 256, stride >= (nbits + 7) / 8).
+  // one_point: `points` holds one point, used for every scalar.  points and
+  // scalars are both host or both device memory (src_dev); dst is flat, host or
+  // device.  `cs` orders the kernels (the caller's stream when a side is device
+  // memory, else the engine's).  Device destination: returns with the work
+  // queued on cs; host destination: returns with the data in dst.
+  void run(hipStream_t cs, const void *points, const uint8_t *scalars, void *dst, size_t n, int nbits, size_t stride,
+           bool one_point, bool src_dev, bool dst_dev);
+  size_t device_bytes() const {
+    return xz_.bytes + rows_.bytes + lv_.bytes + din_[0].bytes + din_[1].bytes + dout_[0].bytes + dout_[1].bytes;
+  }
+  int device() const { return dev_; }
+
+ private:
+  int dev_;
+  DevBuf xz_, rows_, lv_, din_[2], dout_[2];  // xyzz multiples / ladder results, affine rows, tree levels, staging
+  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr};
+  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0;
+  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
+  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
+  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (table and level buffers are reused)
+  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  // the rows of `np` points (row m of point t at rows_[(m - 1) np + t])
+  void table(hipStream_t s, const void *d_points, size_t np);
+  // one chunk, device to device, on a table of np rows per multiple (np == 1: every lane reads point 0's)
+  void ladder(hipStream_t s, size_t np, const uint8_t *d_scalars, void *d_dst, size_t n, int nbits, size_t stride);
+};
+
+}  // namespace msm

@@ -12,7 +12,10 @@
 //              element's inverse (prefix products recomputed into registers,
 //              then back-substitution), written in place over level[l]
 // Level 0 is the Z coordinates, read straight from the blst Jacobians, and the
-// level-0 k_ta_down writes the blst affine output.
+// level-0 k_ta_down writes the blst affine output.  The same tree normalises
+// xyzz points in internal form (ta_tree with TA_XYZZ_BLST / TA_XYZZ_ROWS, used by
+// points_mult.hip): level 0 is then ZZZ, and from 1 / ZZZ the level-0 k_ta_down
+// forms 1 / Z = ZZ / ZZZ, 1 / ZZ = (1 / Z)^2, x = X / ZZ, y = Y / ZZZ (4 products).
 //
 // No layout conversion per coordinate: the stored limbs of a blst coordinate
 // (v 2^384 mod p) are used AS the internal value (internal Montgomery R =
@@ -100,13 +103,15 @@ __device__ __forceinline__ void ta_static_for(Fn &&f) {
   }
 }
 
-// element j of a level: L0 = the Z of Jacobian j (zero -> one, `zero` set;
-// uniform over a lane pair), else level element j
-template <int G, bool L0>
+// element j of a level: SRC = TA_JAC the Z of Jacobian j, an xyzz source the
+// ZZZ of xyzz point j (zero -> one, `zero` set; uniform over a lane pair), else
+// level element j
+template <int G, int SRC>
 __device__ __forceinline__ void ta_elem(typename TaLane<G>::LF &r, const void *lvl, size_t j, int comp, bool &zero) {
   typedef typename TaLane<G>::LF LF;
-  if (L0) {
-    ta_ld_raw(r, static_cast<const uint64_t *>(lvl) + j * 18 * G + 12 * G, comp);
+  if (SRC != TA_LEVEL) {
+    if (SRC == TA_JAC) ta_ld_raw(r, static_cast<const uint64_t *>(lvl) + j * 18 * G + 12 * G, comp);
+    else ta_ld(r, &(static_cast<const Xyzz<typename FieldOf<G>::F> *>(lvl) + j)->zzz, comp);
     zero = f_is_zero_exact(r);
     LF one;
     f_one(one);
@@ -118,7 +123,7 @@ __device__ __forceinline__ void ta_elem(typename TaLane<G>::LF &r, const void *l
 }
 
 // lane (pair) t < n_dst: dst[t] = prod src[8t .. min(8t + 8, n_src))
-template <int G, bool L0>
+template <int G, int SRC>
 static __global__ void __launch_bounds__(128)
     k_ta_up(const void *__restrict__ src, size_t n_src, typename FieldOf<G>::F *__restrict__ dst, size_t n_dst) {
   typedef typename TaLane<G>::LF LF;
@@ -130,10 +135,10 @@ static __global__ void __launch_bounds__(128)
   const size_t cnt = min((size_t)TA_K, n_src - j0);
   bool z;
   LF acc;
-  ta_elem<G, L0>(acc, src, j0, comp, z);
+  ta_elem<G, SRC>(acc, src, j0, comp, z);
   for (size_t j = 1; j < cnt; ++j) {
     LF e;
-    ta_elem<G, L0>(e, src, j0 + j, comp, z);
+    ta_elem<G, SRC>(e, src, j0 + j, comp, z);
     f_mul_bs(acc, acc, e);
   }
   ta_st(dst + t, acc, comp);
@@ -154,12 +159,13 @@ static __global__ void __launch_bounds__(64) k_ta_leaf(typename FieldOf<G>::F *t
 }
 
 // lane (pair) t < n_up: inv_up[t] = 1 / prod lvl[8t ..]; every element of the
-// group is replaced by its inverse (L0: the affine point of Jacobian j is
-// written to out instead, lvl = the Jacobians, read only)
-template <int G, bool L0>
+// group is replaced by its inverse (a point source: the affine point of point j
+// is written to out instead, lvl = the points, read only; TA_XYZZ_ROWS writes
+// canonical internal limbs, Aff<F>, the others blst limbs)
+template <int G, int SRC>
 static __global__ void __launch_bounds__(128)
     k_ta_down(const typename FieldOf<G>::F *__restrict__ inv_up, size_t n_up, void *lvl, size_t n_lvl,
-              uint64_t *out) {
+              void *out) {
   typedef typename TaLane<G>::LF LF;
   typedef typename FieldOf<G>::F SF;
   const size_t tt = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -172,14 +178,14 @@ static __global__ void __launch_bounds__(128)
   ta_ld(I, inv_up + t, comp);
   bool z;
   LF pre[TA_K - 1];  // pre[j] = e_0 .. e_j
-  ta_elem<G, L0>(pre[0], lvl, j0, comp, z);
+  ta_elem<G, SRC>(pre[0], lvl, j0, comp, z);
   // (compile-time steps: a `#pragma unroll` loop guarded by j < cnt is turned
   // into a loop of cnt trips, not unrolled, and pre[] lands in scratch)
   ta_static_for<1, (int)TA_K - 1>([&](auto jc) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
     if (j < cnt) {
       LF e;
-      ta_elem<G, L0>(e, lvl, j0 + j, comp, z);
+      ta_elem<G, SRC>(e, lvl, j0 + j, comp, z);
       f_mul_bs(pre[j], pre[j - 1], e);
     }
   });
@@ -187,16 +193,16 @@ static __global__ void __launch_bounds__(128)
     constexpr int j = (int)TA_K - 1 - decltype(jc)::value;
     if (j < cnt) {
       LF e, ij;
-      ta_elem<G, L0>(e, lvl, j0 + j, comp, z);
+      ta_elem<G, SRC>(e, lvl, j0 + j, comp, z);
       if constexpr (j > 0) {
         f_mul_bs(ij, I, pre[j - 1]);  // 1 / e_j = (1 / (e_0 .. e_j)) (e_0 .. e_{j-1})
         f_mul_bs(I, I, e);
       } else {
         ij = I;
       }
-      if constexpr (L0) {
+      if constexpr (SRC == TA_JAC) {
         const uint64_t *P = static_cast<const uint64_t *>(lvl) + (j0 + j) * 18 * G;
-        uint64_t *o = out + (j0 + j) * 12 * G;
+        uint64_t *o = static_cast<uint64_t *>(out) + (j0 + j) * 12 * G;
         LF zi, zi2, zi3, X, Y, zero;
         ta_mulk(zi, ij);
         f_sqr(zi2, zi);
@@ -212,6 +218,34 @@ static __global__ void __launch_bounds__(128)
         ta_sel(Y, z, zero);
         ta_st_raw(o, X, comp);
         ta_st_raw(o + 6 * G, Y, comp);
+      } else if constexpr (SRC != TA_LEVEL) {
+        const Xyzz<SF> *P = static_cast<const Xyzz<SF> *>(lvl) + j0 + j;
+        LF zi, izz, X, Y, zero;
+        ta_ld(zi, &P->zz, comp);
+        ta_ld(X, &P->x, comp);
+        ta_ld(Y, &P->y, comp);
+        f_mul_bs(zi, zi, ij);  // 1 / Z = ZZ / ZZZ
+        f_sqr(izz, zi);
+        f_mul_bs(X, X, izz);
+        f_mul_bs(Y, Y, ij);
+        if constexpr (SRC == TA_XYZZ_BLST) {  // internal -> blst limbs
+          ta_mulk(X, X);
+          ta_mulk(Y, Y);
+        }
+        f_csub(X);
+        f_csub(Y);
+        f_zero(zero);
+        ta_sel(X, z, zero);
+        ta_sel(Y, z, zero);
+        if constexpr (SRC == TA_XYZZ_BLST) {
+          uint64_t *o = static_cast<uint64_t *>(out) + (j0 + j) * 12 * G;
+          ta_st_raw(o, X, comp);
+          ta_st_raw(o + 6 * G, Y, comp);
+        } else {
+          Aff<SF> *o = static_cast<Aff<SF> *>(out) + j0 + j;
+          ta_st(&o->x, X, comp);
+          ta_st(&o->y, Y, comp);
+        }
       } else {
         ta_st(static_cast<SF *>(lvl) + j0 + j, ij, comp);
       }
@@ -267,37 +301,54 @@ void ToAffine<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
   have = bytes;
 }
 
+// the tree over n points at d_src (kind: TA_JAC, TA_XYZZ_BLST, TA_XYZZ_ROWS), all
+// in device memory; lv holds ta_level_elems(n) elements
+template <int G, int SRC>
+static void ta_tree_k(hipStream_t s, void *lv, size_t lv_bytes, const void *d_src, void *d_dst, size_t n) {
+  typedef typename FieldOf<G>::F SF;
+  const std::vector<size_t> lvs = ta_levels(n);
+  std::vector<SF *> L(lvs.size());
+  size_t off = 0;
+  for (size_t i = 0; i < lvs.size(); ++i) {
+    L[i] = static_cast<SF *>(lv) + off;
+    off += lvs[i];
+  }
+  if (off * sizeof(SF) > lv_bytes) throw std::runtime_error("to_affine: level buffer too small");
+  const unsigned B = 128;
+  hipLaunchKernelGGL((k_ta_up<G, SRC>), dim3(nblk(lvs[0] * G, B)), dim3(B), 0, s, d_src, n, L[0], lvs[0]);
+  MSM_HIP_CHECK(hipGetLastError());
+  for (size_t i = 1; i < lvs.size(); ++i) {
+    hipLaunchKernelGGL((k_ta_up<G, TA_LEVEL>), dim3(nblk(lvs[i] * G, B)), dim3(B), 0, s, (const void *)L[i - 1],
+                       lvs[i - 1], L[i], lvs[i]);
+    MSM_HIP_CHECK(hipGetLastError());
+  }
+  const size_t top = lvs.size() - 1;
+  hipLaunchKernelGGL(k_ta_leaf<G>, dim3(nblk(lvs[top] * G, 64)), dim3(64), 0, s, L[top], lvs[top]);
+  MSM_HIP_CHECK(hipGetLastError());
+  for (size_t i = top; i >= 1; --i) {
+    hipLaunchKernelGGL((k_ta_down<G, TA_LEVEL>), dim3(nblk(lvs[i] * G, B)), dim3(B), 0, s, (const SF *)L[i], lvs[i],
+                       (void *)L[i - 1], lvs[i - 1], (void *)nullptr);
+    MSM_HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL((k_ta_down<G, SRC>), dim3(nblk(lvs[0] * G, B)), dim3(B), 0, s, (const SF *)L[0], lvs[0],
+                     const_cast<void *>(d_src), n, d_dst);
+  MSM_HIP_CHECK(hipGetLastError());
+}
+
+template <int G>
+void ta_tree(hipStream_t s, void *lv, size_t lv_bytes, int kind, const void *d_src, void *d_dst, size_t n) {
+  if (!n) return;
+  if (kind == TA_JAC) ta_tree_k<G, TA_JAC>(s, lv, lv_bytes, d_src, d_dst, n);
+  else if (kind == TA_XYZZ_BLST) ta_tree_k<G, TA_XYZZ_BLST>(s, lv, lv_bytes, d_src, d_dst, n);
+  else if (kind == TA_XYZZ_ROWS) ta_tree_k<G, TA_XYZZ_ROWS>(s, lv, lv_bytes, d_src, d_dst, n);
+  else throw std::runtime_error("to_affine: unknown source kind");
+}
+template void ta_tree<MSM_GROUP>(hipStream_t, void *, size_t, int, const void *, void *, size_t);
+
 // one chunk, device to device: n <= the chunk the level buffer was sized for
 template <int G>
 void ToAffine<G>::kernels(hipStream_t s, const void *d_src, void *d_dst, size_t n) {
-  typedef typename FieldOf<G>::F SF;
-  const std::vector<size_t> lv = ta_levels(n);
-  std::vector<SF *> L(lv.size());
-  size_t off = 0;
-  for (size_t i = 0; i < lv.size(); ++i) {
-    L[i] = lv_.as<SF>() + off;
-    off += lv[i];
-  }
-  if (off * sizeof(SF) > lv_.bytes) throw std::runtime_error("to_affine: level buffer too small");
-  const unsigned B = 128;
-  hipLaunchKernelGGL((k_ta_up<G, true>), dim3(nblk(lv[0] * G, B)), dim3(B), 0, s, d_src, n, L[0], lv[0]);
-  MSM_HIP_CHECK(hipGetLastError());
-  for (size_t i = 1; i < lv.size(); ++i) {
-    hipLaunchKernelGGL((k_ta_up<G, false>), dim3(nblk(lv[i] * G, B)), dim3(B), 0, s, (const void *)L[i - 1],
-                       lv[i - 1], L[i], lv[i]);
-    MSM_HIP_CHECK(hipGetLastError());
-  }
-  const size_t top = lv.size() - 1;
-  hipLaunchKernelGGL(k_ta_leaf<G>, dim3(nblk(lv[top] * G, 64)), dim3(64), 0, s, L[top], lv[top]);
-  MSM_HIP_CHECK(hipGetLastError());
-  for (size_t i = top; i >= 1; --i) {
-    hipLaunchKernelGGL((k_ta_down<G, false>), dim3(nblk(lv[i] * G, B)), dim3(B), 0, s, (const SF *)L[i], lv[i],
-                       (void *)L[i - 1], lv[i - 1], (uint64_t *)nullptr);
-    MSM_HIP_CHECK(hipGetLastError());
-  }
-  hipLaunchKernelGGL((k_ta_down<G, true>), dim3(nblk(lv[0] * G, B)), dim3(B), 0, s, (const SF *)L[0], lv[0],
-                     const_cast<void *>(d_src), n, static_cast<uint64_t *>(d_dst));
-  MSM_HIP_CHECK(hipGetLastError());
+  ta_tree<G>(s, lv_.p, lv_.bytes, TA_JAC, d_src, d_dst, n);
 }
 
 template <int G>

@@ -45,6 +45,27 @@ inline std::vector<size_t> ta_levels(size_t n) {
   return lv;
 }
 
+// total elements of the levels above n points (the size of a level buffer)
+inline size_t ta_level_elems(size_t n) {
+  size_t e = 0;
+  for (size_t v : ta_levels(n)) e += v;
+  return e;
+}
+
+// what level 0 of a tree reads and its last kernel writes
+enum {
+  TA_LEVEL = 0,      // (inside the tree: a level above the points)
+  TA_JAC = 1,        // blst Jacobians -> blst affine points
+  TA_XYZZ_BLST = 2,  // xyzz points in internal form (ec.hpp, Xyzz<F>) -> blst affine points
+  TA_XYZZ_ROWS = 3,  // the same -> canonical affine points in internal form (Aff<F>, 112 G bytes)
+};
+// The whole tree, device to device, on stream s: n points of `kind` at d_src ->
+// n affine points at d_dst; lv: a device buffer of at least ta_level_elems(n)
+// elements of 56 G bytes.  Infinity (Z / ZZZ zero) gives the all-zero point.
+// Defined in to_affine.hip for the group it is compiled for.
+template <int G>
+void ta_tree(hipStream_t s, void *lv, size_t lv_bytes, int kind, const void *d_src, void *d_dst, size_t n);
+
 // One engine: level buffers, and for host memory two pinned + two device
 // staging buffers per direction with their own copy streams.
 template <int G>
