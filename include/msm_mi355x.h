@@ -479,6 +479,39 @@ int msm_points_mult(int group, int device, void *dst_affine, const void *points_
                     size_t npoints, size_t nbits, size_t scalar_stride, int flags, int src_on_device,
                     int dst_on_device, void *hip_stream);
 
+/* ---- bulk point encoding (replaces a loop over the reference's one-point
+ * blst_p{1,2}_affine_compress / _affine_serialize / _compress / _serialize: ref
+ * src/e1.c:139-234 and the src/e2.c twins) ----
+ * src: npoints flat blst affine points (96 G bytes, MSM_SRC_AFFINE) or blst Jacobians
+ * (144 G bytes, MSM_SRC_JACOBIAN), G = group.  dst: npoints ZCash entries of 48 G bytes
+ * (MSM_ENC_COMPRESSED) or 96 G bytes (MSM_ENC_SERIALIZED).  Entry i is byte-identical
+ * to the reference call for its source form and encoding.  Nothing is validated and
+ * there is no status: whatever coordinates are given are encoded, on the curve or not.
+ * Affine infinity is the all-zero point (X zero with Y non-zero is a finite entry), a
+ * Jacobian is infinity when Z is zero whatever X and Y hold; infinity encodes as
+ * c0 00.. / 40 00...  Finite points: canonical big-endian coordinates (G2: imaginary
+ * part first); compressed entries carry 0x80 and, when y is larger than -y (G2: by the
+ * imaginary part unless it is zero), 0x20.  Affine limbs in [p, 2^384) encode their
+ * value mod p (as the reference, whose sign rule counts y limbs that are a non-zero
+ * multiple of p as p itself: flag set, bytes zero); non-canonical Jacobian coordinates
+ * are unspecified.
+ * src and dst each in host or device memory (device src 8-byte, device dst 4-byte
+ * aligned), on HIP device `device`.  flags must be 0.
+ * npoints == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: a NULL
+ * pointer with npoints > 0, group other than 1 or 2, unknown source form, unknown
+ * encoding, non-zero flags, overlapping host ranges.  MSM_E_NODEV: no such device.
+ * MSM_E_HIP: a HIP failure; a host dst is then zero-filled.  Streams as
+ * msm_points_to_affine.  On the GPU: csrc/encode.hip, 2 G field products per affine
+ * point; Jacobians go through the inversion tree of msm_points_to_affine, whose last
+ * kernel writes the entries (no affine array in between); chunks of at most 2^18
+ * points (MSM_ENCODE_CHUNK=<points> overrides, read at each call), host memory through
+ * two pinned staging buffers per direction.  Thread-safe per call (an engine pool
+ * keyed by (device, group), counted by msm_engine_cache_stats(), freed by
+ * msm_release_engine_cache()). */
+enum { MSM_SRC_AFFINE = 0, MSM_SRC_JACOBIAN = 1 };
+int msm_points_encode(int group, int device, void *dst, const void *src, size_t npoints, int src_form, int encoding,
+                      int flags, int src_on_device, int dst_on_device, void *hip_stream);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

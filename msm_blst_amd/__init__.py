@@ -16,6 +16,8 @@ Mirrors:
                                                       (ref e1.c:236-351, e2.c:279-410), bulk, on the GPU
   ps_mult                                             out[i] = [k_i]P_i: a loop over blst_p{1,2}_mult / _unchecked_mult
                                                       (ref e1.c:505-533, ec_mult.h), bulk, on the GPU
+  ps_encode                                           blst_p{1,2}_[affine_]compress / _serialize (ref e1.c:139-234,
+                                                      e2.c), bulk, on the GPU
 """
 import ctypes
 
@@ -25,13 +27,15 @@ from .ches import CHESContext
 from .wbits import WbitsContext
 
 __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext", "p1s_mult_pippenger", "p2s_mult_pippenger", "ps_add", "fixed_points", "gen_scalars",
-           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "ps_mult", "device_count", "lib"]
+           "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "ps_mult", "ps_encode",
+           "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
 JAC_BYTES = {1: 144, 2: 288}
 ENC_COMPRESSED, ENC_SERIALIZED = 0, 1  # MSM_ENC_*: 48 G / 96 G bytes per entry
 DECODE_CHECK_GROUP = 1                 # MSM_DECODE_CHECK_GROUP
 MULT_ONE_POINT = 1                     # MSM_MULT_ONE_POINT
+SRC_AFFINE, SRC_JACOBIAN = 0, 1        # MSM_SRC_*: 96 G / 144 G bytes per point
 
 
 def device_count():
@@ -186,6 +190,37 @@ def ps_mult(group, points, scalars, n, *, nbits=255, stride=32, one_point=False,
     out = (ctypes.c_uint8 * (POINT_BYTES[group] * n))()
     check(lib().msm_points_mult(group, device, out, pts, sc, n, nbits, stride, flags, int(bool(src_on_device)), 0,
                                 stream))
+    return bytes(out)
+
+
+def ps_encode(group, points, n, *, compressed=True, jacobian=False, src_on_device=False, dst=None, device=0,
+              stream=None):
+    """n affine points (96 G bytes each), or Jacobians (144 G bytes, jacobian=True), ->
+    n ZCash entries of 48 G bytes (compressed) or 96 G bytes through msm_points_encode,
+    byte for byte what blst_p{1,2}_[affine_]compress / _serialize give.  Nothing is
+    validated; the all-zero affine point and every Jacobian with Z = 0 are infinity.
+    A host source is a bytes-like object, a device source (src_on_device) a device
+    pointer.  Without dst the entries come back as bytes; with dst=<device pointer>
+    they are written there, ordered on `stream`, and None is returned."""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    form = SRC_JACOBIAN if jacobian else SRC_AFFINE
+    enc = ENC_COMPRESSED if compressed else ENC_SERIALIZED
+    if src_on_device:
+        src = points
+    else:
+        src = _buf(points)
+        have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+        need = n * (JAC_BYTES if jacobian else POINT_BYTES)[group]
+        if have < need:
+            raise ValueError(f"{have} bytes of points given, {need} needed")
+    if dst is not None:
+        check(lib().msm_points_encode(group, device, dst, src, n, form, enc, 0, int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (n * 48 * group * (1 if compressed else 2)))()
+    check(lib().msm_points_encode(group, device, out, src, n, form, enc, 0, int(bool(src_on_device)), 0, stream))
     return bytes(out)
 
 

@@ -130,6 +130,7 @@ def lib():
     L.msm_points_decode.argtypes = [i32, i32, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]
     L.msm_ctx_set_points_encoded.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp]
     L.msm_points_mult.argtypes = [i32, i32, vp, vp, vp, sz, sz, sz, i32, i32, i32, vp]
+    L.msm_points_encode.argtypes = [i32, i32, vp, vp, sz, i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
 

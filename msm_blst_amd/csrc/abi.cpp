@@ -18,6 +18,7 @@
 
 #include "../../include/msm_mi355x.h"
 #include "decode.hpp"
+#include "encode.hpp"
 #include "engine.hpp"
 #include "multi.hpp"
 #include "points_mult.hpp"
@@ -402,6 +403,50 @@ int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t
     if (!dst_dev) memset(dst, 0, n * aff);  // never half written
     if (status) memset(status, 1, n);
     if (nbad) *nbad = n;
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
+// ---- bulk point encoding (a loop over ref e1.c:139-234 and the e2.c twins) ----
+// cs orders the kernels: the caller's stream when a side is device memory, else
+// the leased engine's own.
+template <int G>
+void points_encode(int dev, void *dst, const void *src, size_t n, bool jacobian, bool serialized, bool src_dev,
+                   bool dst_dev, hipStream_t user) {
+  DeviceGuard g(dev);
+  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+  auto eng = EnginePool<Encode<G>>::get().lease(dev, G, [&] { return std::make_unique<Encode<G>>(dev); });
+  const bool on_user = src_dev || dst_dev;
+  hipStream_t cs = on_user ? user : eng->stream();
+  (*eng)->run(cs, src, dst, n, jacobian, serialized, src_dev, dst_dev);
+  // the legacy default stream gives the caller nothing to wait on: finish here
+  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+int points_encode_checked(int group, int dev, void *dst, const void *src, size_t n, int src_form, int encoding,
+                          int flags, bool src_dev, bool dst_dev, hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (src_form != MSM_SRC_AFFINE && src_form != MSM_SRC_JACOBIAN) return fail(MSM_E_ARG, "unknown source form");
+  if (encoding != MSM_ENC_COMPRESSED && encoding != MSM_ENC_SERIALIZED) return fail(MSM_E_ARG, "unknown encoding");
+  if (flags != 0) return fail(MSM_E_ARG, "unknown flag bits");
+  if (n == 0) return MSM_OK;  // nothing touched
+  if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
+  if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
+  const bool jac = src_form == MSM_SRC_JACOBIAN, ser = encoding == MSM_ENC_SERIALIZED;
+  const size_t pt = (size_t)(jac ? 144 : 96) * group, enc = (size_t)(ser ? 96 : 48) * group;
+  if (!src_dev && !dst_dev && ranges_overlap(src, n * pt, dst, n * enc))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (src_dev && ((uintptr_t)src & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 3) != 0) return fail(MSM_E_ARG, "device destination not 4-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    if (group == 1) points_encode<1>(dev, dst, src, n, jac, ser, src_dev, dst_dev, user);
+    else points_encode<2>(dev, dst, src, n, jac, ser, src_dev, dst_dev, user);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (!dst_dev) memset(dst, 0, n * enc);  // never half written
     return fail(MSM_E_HIP, e.what());
   }
 }
@@ -825,6 +870,12 @@ int msm_points_mult(int group, int device, void *dst, const void *points, const 
                     void *hip_stream) {
   return points_mult_checked(group, device, dst, points, scalars, npoints, nbits, scalar_stride, flags,
                              src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_points_encode(int group, int device, void *dst, const void *src, size_t npoints, int src_form, int encoding,
+                      int flags, int src_on_device, int dst_on_device, void *hip_stream) {
+  return points_encode_checked(group, device, dst, src, npoints, src_form, encoding, flags, src_on_device != 0,
+                               dst_on_device != 0, (hipStream_t)hip_stream);
 }
 
 const char *msm_last_error(void) { return g_err.c_str(); }

@@ -16,6 +16,9 @@
 // xyzz points in internal form (ta_tree with TA_XYZZ_BLST / TA_XYZZ_ROWS, used by
 // points_mult.hip): level 0 is then ZZZ, and from 1 / ZZZ the level-0 k_ta_down
 // forms 1 / Z = ZZ / ZZZ, 1 / ZZ = (1 / Z)^2, x = X / ZZ, y = Y / ZZZ (4 products).
+// The bulk encoder (encode.hip) runs the tree with TA_JAC_ENC_C / TA_JAC_ENC_S:
+// the level-0 k_ta_down then hands x and y to the encoder's tail (encode_dev.hpp)
+// and writes ZCash entries, with no affine array in between.
 //
 // No layout conversion per coordinate: the stored limbs of a blst coordinate
 // (v 2^384 mod p) are used AS the internal value (internal Montgomery R =
@@ -41,6 +44,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "encode_dev.hpp"
 #include "pair_kernels.hpp"
 
 #ifndef MSM_GROUP
@@ -94,6 +98,8 @@ __device__ __forceinline__ void ta_sel(Fp &r, bool c, const Fp &a) {  // r = c ?
   for (int i = 0; i < NL; ++i) r.v[i] = c ? a.v[i] : r.v[i];
 }
 __device__ __forceinline__ void ta_sel(Fp2L &r, bool c, const Fp2L &a) { ta_sel(r.c, c, a.c); }
+__device__ __forceinline__ const Fp &ta_c(const Fp &a) { return a; }
+__device__ __forceinline__ const Fp &ta_c(const Fp2L &a) { return a.c; }
 
 template <int J, int N, class Fn>
 __device__ __forceinline__ void ta_static_for(Fn &&f) {
@@ -103,14 +109,17 @@ __device__ __forceinline__ void ta_static_for(Fn &&f) {
   }
 }
 
-// element j of a level: SRC = TA_JAC the Z of Jacobian j, an xyzz source the
+// the kinds whose level 0 is the Z of blst Jacobians
+constexpr bool ta_is_jac(int src) { return src == TA_JAC || src == TA_JAC_ENC_C || src == TA_JAC_ENC_S; }
+
+// element j of a level: a Jacobian kind the Z of Jacobian j, an xyzz source the
 // ZZZ of xyzz point j (zero -> one, `zero` set; uniform over a lane pair), else
 // level element j
 template <int G, int SRC>
 __device__ __forceinline__ void ta_elem(typename TaLane<G>::LF &r, const void *lvl, size_t j, int comp, bool &zero) {
   typedef typename TaLane<G>::LF LF;
   if (SRC != TA_LEVEL) {
-    if (SRC == TA_JAC) ta_ld_raw(r, static_cast<const uint64_t *>(lvl) + j * 18 * G + 12 * G, comp);
+    if (ta_is_jac(SRC)) ta_ld_raw(r, static_cast<const uint64_t *>(lvl) + j * 18 * G + 12 * G, comp);
     else ta_ld(r, &(static_cast<const Xyzz<typename FieldOf<G>::F> *>(lvl) + j)->zzz, comp);
     zero = f_is_zero_exact(r);
     LF one;
@@ -218,6 +227,20 @@ static __global__ void __launch_bounds__(128)
         ta_sel(Y, z, zero);
         ta_st_raw(o, X, comp);
         ta_st_raw(o + 6 * G, Y, comp);
+      } else if constexpr (ta_is_jac(SRC)) {  // the encoded kinds: the same x, y, then the encoder's tail
+        constexpr bool SER = SRC == TA_JAC_ENC_S;
+        const uint64_t *P = static_cast<const uint64_t *>(lvl) + (j0 + j) * 18 * G;
+        LF zi, zi2, zi3, X, Y;
+        ta_mulk(zi, ij);
+        f_sqr(zi2, zi);
+        f_mul_bs(zi3, zi2, zi);
+        ta_ld_raw(X, P, comp);
+        ta_ld_raw(Y, P + 6 * G, comp);
+        f_mul_bs(X, X, zi2);
+        f_mul_bs(Y, Y, zi3);
+        f_csub(X);  // the canonical blst limbs the reference's own normalisation hands its encoder
+        f_csub(Y);
+        enc_entry<G, SER>(static_cast<uint8_t *>(out) + (j0 + j) * (SER ? 96 : 48) * G, ta_c(X), ta_c(Y), z, comp);
       } else if constexpr (SRC != TA_LEVEL) {
         const Xyzz<SF> *P = static_cast<const Xyzz<SF> *>(lvl) + j0 + j;
         LF zi, izz, X, Y, zero;
@@ -301,7 +324,7 @@ void ToAffine<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
   have = bytes;
 }
 
-// the tree over n points at d_src (kind: TA_JAC, TA_XYZZ_BLST, TA_XYZZ_ROWS), all
+// the tree over n points at d_src (kind: every point source of to_affine.hpp), all
 // in device memory; lv holds ta_level_elems(n) elements
 template <int G, int SRC>
 static void ta_tree_k(hipStream_t s, void *lv, size_t lv_bytes, const void *d_src, void *d_dst, size_t n) {
@@ -315,7 +338,8 @@ static void ta_tree_k(hipStream_t s, void *lv, size_t lv_bytes, const void *d_sr
   }
   if (off * sizeof(SF) > lv_bytes) throw std::runtime_error("to_affine: level buffer too small");
   const unsigned B = 128;
-  hipLaunchKernelGGL((k_ta_up<G, SRC>), dim3(nblk(lvs[0] * G, B)), dim3(B), 0, s, d_src, n, L[0], lvs[0]);
+  constexpr int UP = ta_is_jac(SRC) ? (int)TA_JAC : SRC;  // the way up reads Z alone
+  hipLaunchKernelGGL((k_ta_up<G, UP>), dim3(nblk(lvs[0] * G, B)), dim3(B), 0, s, d_src, n, L[0], lvs[0]);
   MSM_HIP_CHECK(hipGetLastError());
   for (size_t i = 1; i < lvs.size(); ++i) {
     hipLaunchKernelGGL((k_ta_up<G, TA_LEVEL>), dim3(nblk(lvs[i] * G, B)), dim3(B), 0, s, (const void *)L[i - 1],
@@ -341,6 +365,8 @@ void ta_tree(hipStream_t s, void *lv, size_t lv_bytes, int kind, const void *d_s
   if (kind == TA_JAC) ta_tree_k<G, TA_JAC>(s, lv, lv_bytes, d_src, d_dst, n);
   else if (kind == TA_XYZZ_BLST) ta_tree_k<G, TA_XYZZ_BLST>(s, lv, lv_bytes, d_src, d_dst, n);
   else if (kind == TA_XYZZ_ROWS) ta_tree_k<G, TA_XYZZ_ROWS>(s, lv, lv_bytes, d_src, d_dst, n);
+  else if (kind == TA_JAC_ENC_C) ta_tree_k<G, TA_JAC_ENC_C>(s, lv, lv_bytes, d_src, d_dst, n);
+  else if (kind == TA_JAC_ENC_S) ta_tree_k<G, TA_JAC_ENC_S>(s, lv, lv_bytes, d_src, d_dst, n);
   else throw std::runtime_error("to_affine: unknown source kind");
 }
 template void ta_tree<MSM_GROUP>(hipStream_t, void *, size_t, int, const void *, void *, size_t);

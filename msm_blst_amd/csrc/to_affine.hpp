@@ -58,10 +58,13 @@ enum {
   TA_JAC = 1,        // blst Jacobians -> blst affine points
   TA_XYZZ_BLST = 2,  // xyzz points in internal form (ec.hpp, Xyzz<F>) -> blst affine points
   TA_XYZZ_ROWS = 3,  // the same -> canonical affine points in internal form (Aff<F>, 112 G bytes)
+  TA_JAC_ENC_C = 4,  // blst Jacobians -> compressed ZCash entries (48 G bytes, encode_dev.hpp)
+  TA_JAC_ENC_S = 5,  // blst Jacobians -> serialized ZCash entries (96 G bytes)
 };
 // The whole tree, device to device, on stream s: n points of `kind` at d_src ->
 // n affine points at d_dst; lv: a device buffer of at least ta_level_elems(n)
-// elements of 56 G bytes.  Infinity (Z / ZZZ zero) gives the all-zero point.
+// elements of 56 G bytes.  Infinity (Z / ZZZ zero) gives the all-zero point
+// (the encoded kinds: the infinity entry, c0 00.. / 40 00..; d_dst 4-byte aligned).
 // Defined in to_affine.hip for the group it is compiled for.
 template <int G>
 void ta_tree(hipStream_t s, void *lv, size_t lv_bytes, int kind, const void *d_src, void *d_dst, size_t n);
