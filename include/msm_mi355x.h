@@ -479,6 +479,59 @@ int msm_points_mult(int group, int device, void *dst_affine, const void *points_
                     size_t npoints, size_t nbits, size_t scalar_stride, int flags, int src_on_device,
                     int dst_on_device, void *hip_stream);
 
+/* ---- segmented sums and MSMs over many point sets (replaces a host loop over the
+ * reference's blst_p{1,2}s_mult_pippenger / blst_p{1,2}s_add, one call per point set:
+ * ref src/multi_scalar.c:581-607, src/bulk_addition.c:145-164) ----
+ * With o = offsets and k = nsegments:
+ *   dst[j] = sum over o[j] <= i < o[j + 1] of [k_i] P_i        for j < k,
+ * each a canonical affine point in blst Montgomery layout (infinity: all zero).
+ * offsets is always a HOST array of k + 1 values, non-decreasing.  o[k] points and
+ * scalars are read, indexed from 0; those below o[0] are ignored.  An empty segment
+ * gives infinity.  P_i: affine point i of points_affine; an all-zero point is infinity
+ * and contributes nothing.  scalars == NULL means plain sums, every k_i = 1 (nbits and
+ * scalar_stride are then ignored).  Otherwise k_i, nbits and scalar_stride are exactly
+ * as in msm_points_mult: the low nbits bits of the little-endian scalar at scalars +
+ * i scalar_stride, 0 <= nbits <= 256, (nbits + 7) / 8 <= scalar_stride <= 2^20, stray
+ * bits in the last byte masked, no byte beyond (nbits + 7) / 8 of a scalar read;
+ * nbits == 0 makes every result infinity.
+ * The result is exact for every point of the curve, in the prime-order subgroup or not
+ * (the contract of msm_points_mult; no endomorphism split is used).
+ * points and scalars are both in host memory or both in device memory (src_on_device;
+ * device points 8-byte aligned, scalars unaligned); dst in host or device memory
+ * (8-byte aligned), on HIP device `device`.  flags must be 0.
+ * nsegments == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: NULL
+ * dst / points / offsets with nsegments > 0, a decreasing offset, group other than 1
+ * or 2, nbits > 256, a scalar_stride shorter than (nbits + 7) / 8, non-zero flags, a
+ * host dst overlapping a host source.  MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP
+ * failure; a host dst is then zero-filled.  Streams as msm_points_to_affine.
+ * On the GPU: csrc/point_segments.hip.  The host cuts the points into pieces of at
+ * most L consecutive points of one segment; one lane (G2: a lane pair) runs a Straus
+ * ladder over signed 4-bit windows on the per-point table of msm_points_mult, with
+ * the four doublings of a window shared by the points of its piece (plain sums: one
+ * pass of mixed additions, no table); the partial sums of a segment are merged by a
+ * pairwise tree and the k sums normalised by the inversion tree of
+ * msm_points_to_affine.  L grows with the number of points until the pieces would no
+ * longer fill the chip, 1 <= L <= 64 (MSM_POINTS_SEGMENTS_PIECE=<points> overrides);
+ * chunks are sized by the device memory they allocate, about 3 GiB
+ * (MSM_POINTS_SEGMENTS_CHUNK=<points> overrides; both read at each call); a segment
+ * may span chunks.  Host memory goes through two pinned staging buffers per direction.
+ * There is no bucket method inside a segment: a single very long segment is better
+ * served by a context (msm_ctx_mult and its kin).  For encoded output chain
+ * msm_points_encode on a device dst.  Thread-safe per call (an engine pool keyed by
+ * (device, group), counted by msm_engine_cache_stats(), freed by
+ * msm_release_engine_cache()). */
+int msm_points_msm_segments(int group, int device, void *dst_affine, const void *points_affine, const byte *scalars,
+                            const size_t *offsets, size_t nsegments, size_t nbits, size_t scalar_stride, int flags,
+                            int src_on_device, int dst_on_device, void *hip_stream);
+/* host only, no device work: the piece length L a call over npoints points would use */
+size_t msm_segments_piece(int group, size_t npoints);
+/* host only, no device work: the pieces that `piece` (> 0) cuts offsets into, in
+ * order.  *npieces receives their number; the first `capacity` of them are written to
+ * start[] (first point), count[] (points, <= piece) and segment[] (each may be NULL).
+ * MSM_E_ARG: NULL npieces / offsets, piece == 0, a decreasing offset. */
+int msm_segments_plan(const size_t *offsets, size_t nsegments, size_t piece, size_t *npieces, size_t *start,
+                      size_t *count, size_t *segment, size_t capacity);
+
 /* ---- bulk point encoding (replaces a loop over the reference's one-point
  * blst_p{1,2}_affine_compress / _affine_serialize / _compress / _serialize: ref
  * src/e1.c:139-234 and the src/e2.c twins) ----

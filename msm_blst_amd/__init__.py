@@ -18,6 +18,9 @@ Mirrors:
                                                       (ref e1.c:505-533, ec_mult.h), bulk, on the GPU
   ps_encode                                           blst_p{1,2}_[affine_]compress / _serialize (ref e1.c:139-234,
                                                       e2.c), bulk, on the GPU
+  ps_msm_segments, ps_sum_segments                    k MSMs / k sums over k point sets in one call: a loop over
+                                                      blst_p{1,2}s_mult_pippenger / blst_p{1,2}s_add per set (ref
+                                                      multi_scalar.c:581-607, bulk_addition.c:145-164), on the GPU
 """
 import ctypes
 
@@ -28,6 +31,7 @@ from .wbits import WbitsContext
 
 __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext", "p1s_mult_pippenger", "p2s_mult_pippenger", "ps_add", "fixed_points", "gen_scalars",
            "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "ps_mult", "ps_encode",
+           "ps_msm_segments", "ps_sum_segments", "segments_plan",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -222,6 +226,86 @@ def ps_encode(group, points, n, *, compressed=True, jacobian=False, src_on_devic
     out = (ctypes.c_uint8 * (n * 48 * group * (1 if compressed else 2)))()
     check(lib().msm_points_encode(group, device, out, src, n, form, enc, 0, int(bool(src_on_device)), 0, stream))
     return bytes(out)
+
+
+def _segments(group, points, scalars, offsets, nbits, stride, src_on_device, dst, device, stream):
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    offs = [int(v) for v in offsets]
+    if not offs:
+        raise ValueError("offsets must hold nsegments + 1 values")
+    if offs[0] < 0 or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError("offsets must be non-negative and non-decreasing")
+    k = len(offs) - 1
+    n = offs[-1] if k else 0  # no segment: nothing is read
+    nb = 0
+    if scalars is not None:
+        if not 0 <= nbits <= 256:
+            raise ValueError("nbits must be in [0, 256]")
+        nb = (nbits + 7) // 8
+        if stride < nb:
+            raise ValueError(f"stride {stride} shorter than the {nb} bytes of a {nbits}-bit scalar")
+    else:
+        nbits = stride = 0
+    if src_on_device:
+        pts, sc = points, scalars
+    else:
+        pts = _buf(points)
+        have = len(pts) if hasattr(pts, "__len__") else ctypes.sizeof(pts)
+        if have < POINT_BYTES[group] * n:
+            raise ValueError(f"{have} bytes of points given, {POINT_BYTES[group] * n} needed")
+        sc = None
+        if scalars is not None:
+            sc = _buf(scalars)
+            have = len(sc) if hasattr(sc, "__len__") else ctypes.sizeof(sc)
+            need = (n - 1) * stride + nb if n else 0
+            if have < need:
+                raise ValueError(f"{have} bytes of scalars given, {need} needed")
+    o = (ctypes.c_size_t * (k + 1))(*offs)
+    if dst is not None:
+        check(lib().msm_points_msm_segments(group, device, dst, pts, sc, o, k, nbits, stride, 0,
+                                            int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (POINT_BYTES[group] * k))()
+    check(lib().msm_points_msm_segments(group, device, out, pts, sc, o, k, nbits, stride, 0, int(bool(src_on_device)),
+                                        0, stream))
+    return bytes(out)
+
+
+def ps_msm_segments(group, points, scalars, offsets, *, nbits=255, stride=32, src_on_device=False, dst=None, device=0,
+                    stream=None):
+    """k MSMs over k point sets in one call (msm_points_msm_segments): out[j] = the sum
+    over offsets[j] <= i < offsets[j + 1] of [k_i] P_i, as k affine points (infinity, and
+    every empty segment, is the all-zero point).  offsets: any sequence of k + 1
+    non-decreasing ints; offsets[-1] points and scalars are read, those below offsets[0]
+    ignored.  k_i, nbits and stride as in ps_mult; the result is exact for every point
+    of the curve.  Host sources are bytes-like objects, device sources (src_on_device,
+    both) device pointers.  With dst=<device pointer> the points are written there,
+    ordered on `stream`, and None is returned."""
+    if scalars is None:
+        raise ValueError("scalars missing (ps_sum_segments sums without scalars)")
+    return _segments(group, points, scalars, offsets, nbits, stride, src_on_device, dst, device, stream)
+
+
+def ps_sum_segments(group, points, offsets, *, src_on_device=False, dst=None, device=0, stream=None):
+    """k sums over k point sets in one call (msm_points_msm_segments without scalars):
+    out[j] = the sum of the points offsets[j] <= i < offsets[j + 1]; a loop over
+    blst_p{1,2}s_add with the results made affine.  Arguments as ps_msm_segments."""
+    return _segments(group, points, None, offsets, 0, 0, src_on_device, dst, device, stream)
+
+
+def segments_plan(offsets, piece):
+    """The pieces (start, count, segment) that a piece length cuts offsets into
+    (msm_segments_plan; host only)."""
+    offs = [int(v) for v in offsets]
+    k = len(offs) - 1
+    o = (ctypes.c_size_t * (k + 1))(*offs)
+    npieces = ctypes.c_size_t(0)
+    check(lib().msm_segments_plan(o, k, piece, ctypes.byref(npieces), None, None, None, 0))
+    n = npieces.value
+    st, ct, sg = ((ctypes.c_size_t * max(n, 1))() for _ in range(3))
+    check(lib().msm_segments_plan(o, k, piece, ctypes.byref(npieces), st, ct, sg, n))
+    return [(st[i], ct[i], sg[i]) for i in range(n)]
 
 
 def to_affine_levels(n):

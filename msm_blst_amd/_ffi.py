@@ -131,6 +131,10 @@ def lib():
     L.msm_ctx_set_points_encoded.argtypes = [vp, vp, sz, i32, i32, i32, vp, vp]
     L.msm_points_mult.argtypes = [i32, i32, vp, vp, vp, sz, sz, sz, i32, i32, i32, vp]
     L.msm_points_encode.argtypes = [i32, i32, vp, vp, sz, i32, i32, i32, i32, i32, vp]
+    L.msm_points_msm_segments.argtypes = [i32, i32, vp, vp, vp, vp, sz, sz, sz, i32, i32, i32, vp]
+    L.msm_segments_piece.argtypes = [i32, sz]
+    L.msm_segments_piece.restype = sz
+    L.msm_segments_plan.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz]
     _lib = L
     return L
 

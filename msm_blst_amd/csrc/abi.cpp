@@ -21,6 +21,7 @@
 #include "encode.hpp"
 #include "engine.hpp"
 #include "multi.hpp"
+#include "point_segments.hpp"
 #include "points_mult.hpp"
 #include "pool.hpp"
 #include "ptr_walk.hpp"
@@ -501,6 +502,64 @@ int points_mult_checked(int group, int dev, void *dst, const void *points, const
   }
 }
 
+// ---- segmented sums and MSMs (a loop over ref multi_scalar.c:581-607 / bulk_addition.c:145-164 per point set) ----
+// cs orders the kernels: the caller's stream when a side is device memory, else
+// the leased engine's own.
+template <int G>
+void points_segments(int dev, void *dst, const void *points, const uint8_t *scalars, const size_t *offsets, size_t k,
+                     int nbits, size_t stride, bool src_dev, bool dst_dev, hipStream_t user) {
+  DeviceGuard g(dev);
+  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+  if ((scalars && nbits == 0) || offsets[k] == offsets[0]) {  // every scalar is zero, or every segment is empty
+    if (dst_dev) MSM_HIP_CHECK(hipMemsetAsync(dst, 0, k * 96 * G, user));
+    else memset(dst, 0, k * 96 * G);
+    if (dst_dev && !user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+    return;
+  }
+  auto eng = EnginePool<PointSegments<G>>::get().lease(dev, G, [&] { return std::make_unique<PointSegments<G>>(dev); });
+  const bool on_user = src_dev || dst_dev;
+  hipStream_t cs = on_user ? user : eng->stream();
+  (*eng)->run(cs, points, scalars, offsets, k, dst, nbits, stride, src_dev, dst_dev);
+  // the legacy default stream gives the caller nothing to wait on: finish here
+  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+int points_segments_checked(int group, int dev, void *dst, const void *points, const byte *scalars,
+                            const size_t *offsets, size_t k, size_t nbits, size_t stride, int flags, bool src_dev,
+                            bool dst_dev, hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (scalars) {
+    if (nbits > 256) return fail(MSM_E_ARG, "nbits must be at most 256");
+    if (stride < (nbits + 7) / 8) return fail(MSM_E_ARG, "scalar_stride shorter than (nbits + 7) / 8");
+    if (stride > ((size_t)1 << 20)) return fail(MSM_E_ARG, "scalar_stride out of range");
+  }
+  if (flags != 0) return fail(MSM_E_ARG, "unknown flag bits");
+  if (k == 0) return MSM_OK;  // nothing touched
+  if (!dst || !points || !offsets) return fail(MSM_E_ARG, "null dst / points / offsets");
+  if (k > ((size_t)1 << 40)) return fail(MSM_E_ARG, "nsegments out of range");
+  if (!seg_offsets_ok(offsets, k)) return fail(MSM_E_ARG, "offsets decrease");
+  const size_t n = offsets[k];
+  if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "offsets out of range");
+  const size_t aff = (size_t)96 * group;
+  if (!src_dev && !dst_dev && n > offsets[0] &&
+      (ranges_overlap(points, n * aff, dst, k * aff) ||
+       (scalars && nbits && ranges_overlap(scalars, (n - 1) * stride + (nbits + 7) / 8, dst, k * aff))))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (src_dev && ((uintptr_t)points & 7) != 0) return fail(MSM_E_ARG, "device points not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    if (group == 1) points_segments<1>(dev, dst, points, scalars, offsets, k, (int)nbits, stride, src_dev, dst_dev, user);
+    else points_segments<2>(dev, dst, points, scalars, offsets, k, (int)nbits, stride, src_dev, dst_dev, user);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (!dst_dev) memset(dst, 0, k * aff);  // never half written
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   size_t w = 0;
   while (n >>= 1) ++w;
@@ -876,6 +935,36 @@ int msm_points_encode(int group, int device, void *dst, const void *src, size_t 
                       int flags, int src_on_device, int dst_on_device, void *hip_stream) {
   return points_encode_checked(group, device, dst, src, npoints, src_form, encoding, flags, src_on_device != 0,
                                dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_points_msm_segments(int group, int device, void *dst_affine, const void *points_affine, const byte *scalars,
+                            const size_t *offsets, size_t nsegments, size_t nbits, size_t scalar_stride, int flags,
+                            int src_on_device, int dst_on_device, void *hip_stream) {
+  return points_segments_checked(group, device, dst_affine, points_affine, scalars, offsets, nsegments, nbits,
+                                 scalar_stride, flags, src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+size_t msm_segments_piece(int group, size_t npoints) {
+  if (group != 1 && group != 2) return 0;
+  return seg_piece_len(std::min(npoints, seg_chunk(group)), group);
+}
+
+int msm_segments_plan(const size_t *offsets, size_t nsegments, size_t piece, size_t *npieces, size_t *start,
+                      size_t *count, size_t *segment, size_t capacity) {
+  if (!npieces || piece == 0 || (nsegments && !offsets)) return fail(MSM_E_ARG, "null npieces / offsets or piece == 0");
+  if (!seg_offsets_ok(offsets, nsegments)) return fail(MSM_E_ARG, "offsets decrease");
+  size_t w = 0;
+  *npieces = nsegments ? seg_cut(offsets, nsegments, piece, offsets[0], offsets[nsegments], 0,
+                                 [&](size_t s, size_t c, size_t j) {
+                                   if (w < capacity) {
+                                     if (start) start[w] = s;
+                                     if (count) count[w] = c;
+                                     if (segment) segment[w] = j;
+                                   }
+                                   ++w;
+                                 })
+                       : 0;
+  return MSM_OK;
 }
 
 const char *msm_last_error(void) { return g_err.c_str(); }

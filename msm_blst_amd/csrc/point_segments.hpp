@@ -1,0 +1,69 @@
+// point_segments.hpp -- segmented sums and MSMs on the GPU:
+// dst[j] = sum over offsets[j] <= i < offsets[j + 1] of [k_i] P_i
+// (replaces a host loop over the reference's blst_p{1,2}s_mult_pippenger /
+// blst_p{1,2}s_add, one call per point set: ref src/multi_scalar.c:581-607,
+// src/bulk_addition.c:145-164; kernels and orchestration in point_segments.hip,
+// the host plan in segments_plan.hpp).  This header is host-only.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "engine.hpp"
+#include "segments_plan.hpp"
+
+namespace msm {
+
+// what a lane (pair) of the kernels knows about its partial sum
+struct SegMeta {
+  uint32_t start, count;  // the piece: first point (relative to the chunk) and points; the carried partial has none
+  uint32_t rel, len;      // position in the run of partials of its segment, and the length of that run
+};
+
+// One engine: the table of a chunk (xyzz multiples, then their affine rows; the
+// partial sums reuse the xyzz buffer), the segment results, the level buffer of
+// the shared inversion tree (to_affine.hpp), the partial carried from one chunk
+// into the next, the plan of a chunk (two pinned slots, one device copy), and
+// for host memory two pinned + two device staging buffers per direction with
+// their own copy streams.  A staged input slot holds the points followed by
+// the scalars, packed (nbits + 7) / 8 bytes apart.
+template <int G>
+class PointSegments {
+ public:
+  static constexpr size_t AFF = 96 * G, ROW = 112 * G, XYZZ = 224 * G, ELEM = 56 * G;
+  explicit PointSegments(int device);
+  ~PointSegments();
+  PointSegments(const PointSegments &) = delete;
+  PointSegments &operator=(const PointSegments &) = delete;
+  // dst[j] = sum_{o[j] <= i < o[j + 1]} [k_i] P_i for j < k, o = offsets (host,
+  // k + 1 values, non-decreasing).  k_i = the low nbits bits of the
+  // little-endian scalar at scalars + i stride (0 < nbits <= 256, stride >=
+  // (nbits + 7) / 8), or 1 when scalars is NULL.  points and scalars are both
+  // host or both device memory (src_dev) and are indexed from point 0; dst is
+  // flat, host or device.  `cs` orders the kernels (the caller's stream when a
+  // side is device memory, else the engine's).  Device destination: returns
+  // with the work queued on cs; host destination: returns with the data in dst.
+  void run(hipStream_t cs, const void *points, const uint8_t *scalars, const size_t *offsets, size_t k, void *dst,
+           int nbits, size_t stride, bool src_dev, bool dst_dev);
+  size_t device_bytes() const {
+    return xz_.bytes + rows_.bytes + res_.bytes + lv_.bytes + carry_.bytes + dmeta_.bytes + din_[0].bytes +
+           din_[1].bytes + dout_[0].bytes + dout_[1].bytes;
+  }
+  int device() const { return dev_; }
+
+ private:
+  int dev_;
+  DevBuf xz_, rows_, res_, lv_, carry_, dmeta_, din_[2], dout_[2];
+  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr}, *pin_meta_[2] = {nullptr, nullptr};
+  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0, pin_meta_bytes_ = 0;
+  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
+  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
+  hipEvent_t ev_meta_[2] = {nullptr, nullptr};  // the plan of chunk k - 2 has left its pinned slot
+  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (table, partial and level buffers are reused)
+  std::vector<SegMeta> meta_;     // the plan of the chunk being queued
+  std::vector<uint32_t> src_;     // per segment written by the chunk: the partial that holds its sum, or ~0 (empty)
+  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+};
+
+}  // namespace msm
