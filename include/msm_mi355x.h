@@ -565,6 +565,49 @@ enum { MSM_SRC_AFFINE = 0, MSM_SRC_JACOBIAN = 1 };
 int msm_points_encode(int group, int device, void *dst, const void *src, size_t npoints, int src_form, int encoding,
                       int flags, int src_on_device, int dst_on_device, void *hip_stream);
 
+/* ---- bulk hash-to-curve (replaces a loop over the reference's one-message
+ * blst_hash_to_g{1,2} / blst_encode_to_g{1,2} / blst_map_to_g{1,2}: ref
+ * src/map_to_g1.c:285-453, src/map_to_g2.c:173-401, src/hash_to_field.c:51-154;
+ * RFC 9380, expand_message_xmd over SHA-256, simplified SWU, 11- / 3-isogeny) ----
+ * msm_points_map: u holds npoints * count field elements in blst's Montgomery layout
+ * (48 G bytes each, blst_fp / blst_fp2), canonical; nothing is validated.  count is 1
+ * or 2.  dst[i] is the affine form of blst_map_to_g{1,2}(u[i count], count == 2 ?
+ * u[i count + 1] : NULL), byte for byte; infinity is the all-zero point.
+ * msm_hash_to_field: message i is msgs[offsets[i] .. offsets[i + 1]), offsets a HOST
+ * array of npoints + 1 non-decreasing values, or, with offsets NULL, the msg_len bytes
+ * at msgs + i msg_len.  aug is NULL or npoints * aug_len bytes in the memory space of
+ * msgs; slice i is hashed in front of message i (the reference's aug argument).  DST
+ * is host memory of any length (longer than 255 bytes: replaced once per call by its
+ * SHA-256 under "H2C-OVERSIZE-DST-").  dst receives npoints * count elements in the
+ * layout above: what the reference's hash_to_field(elems, count G, ..) yields.
+ * msm_points_hash: msm_hash_to_field followed by msm_points_map without leaving the
+ * device; MSM_H2C_ENCODE selects count = 1 (blst_encode_to_g{1,2}, non-uniform), else
+ * count = 2 (blst_hash_to_g{1,2}, the random-oracle variant).
+ * u / msgs / aug (one memory space) and dst each in host or device memory (device u and
+ * dst 8-byte aligned), on HIP device `device`.
+ * npoints == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: a NULL
+ * dst, u, or msgs where bytes are needed, group other than 1 or 2, count other than 1
+ * or 2, a decreasing offset, unknown flag bits, a host dst overlapping a host source.
+ * MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP failure; a host dst is then
+ * zero-filled.  Streams as msm_points_to_affine.  On the GPU: csrc/hash_to_curve.hip
+ * (DESIGN section 19); chunks of at most 2^18 entries (MSM_H2C_CHUNK=<entries>
+ * overrides, read at each call), host memory through two pinned staging buffers per
+ * direction.  Thread-safe per call (an engine pool keyed by (device, group), counted by
+ * msm_engine_cache_stats(), freed by msm_release_engine_cache()). */
+enum { MSM_H2C_ENCODE = 1 }; /* flags of msm_points_hash */
+int msm_points_map(int group, int device, void *dst_affine, const void *u, size_t npoints, int count,
+                   int src_on_device, int dst_on_device, void *hip_stream);
+int msm_hash_to_field(int group, int device, void *dst_elems, const void *msgs, const size_t *offsets, size_t msg_len,
+                      const void *aug, size_t aug_len, size_t npoints, const byte *DST, size_t DST_len, int count,
+                      int src_on_device, int dst_on_device, void *hip_stream);
+int msm_points_hash(int group, int device, void *dst_affine, const void *msgs, const size_t *offsets, size_t msg_len,
+                    const void *aug, size_t aug_len, size_t npoints, const byte *DST, size_t DST_len, int flags,
+                    int src_on_device, int dst_on_device, void *hip_stream);
+/* host only, no device work: DST_prime = DST || I2OSP(len, 1) after the oversize rule.
+ * out holds at least 256 bytes; *out_len receives the length.  MSM_E_ARG: NULL out /
+ * out_len, NULL DST with DST_len > 0. */
+int msm_h2c_dst_prime(byte *out, size_t *out_len, const byte *DST, size_t DST_len);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

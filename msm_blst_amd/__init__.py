@@ -21,6 +21,9 @@ Mirrors:
   ps_msm_segments, ps_sum_segments                    k MSMs / k sums over k point sets in one call: a loop over
                                                       blst_p{1,2}s_mult_pippenger / blst_p{1,2}s_add per set (ref
                                                       multi_scalar.c:581-607, bulk_addition.c:145-164), on the GPU
+  ps_hash_to_curve, ps_hash_to_field, ps_map_to_curve blst_hash_to_g{1,2} / blst_encode_to_g{1,2} / blst_map_to_g{1,2} and
+                                                      hash_to_field (ref map_to_g1.c:285-453, map_to_g2.c:173-401,
+                                                      hash_to_field.c:51-154), bulk, on the GPU
 """
 import ctypes
 
@@ -32,6 +35,7 @@ from .wbits import WbitsContext
 __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext", "p1s_mult_pippenger", "p2s_mult_pippenger", "ps_add", "fixed_points", "gen_scalars",
            "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "ps_mult", "ps_encode",
            "ps_msm_segments", "ps_sum_segments", "segments_plan",
+           "ps_map_to_curve", "ps_hash_to_field", "ps_hash_to_curve", "h2c_dst_prime",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -40,6 +44,7 @@ ENC_COMPRESSED, ENC_SERIALIZED = 0, 1  # MSM_ENC_*: 48 G / 96 G bytes per entry
 DECODE_CHECK_GROUP = 1                 # MSM_DECODE_CHECK_GROUP
 MULT_ONE_POINT = 1                     # MSM_MULT_ONE_POINT
 SRC_AFFINE, SRC_JACOBIAN = 0, 1        # MSM_SRC_*: 96 G / 144 G bytes per point
+H2C_ENCODE = 1                         # MSM_H2C_ENCODE
 
 
 def device_count():
@@ -306,6 +311,144 @@ def segments_plan(offsets, piece):
     st, ct, sg = ((ctypes.c_size_t * max(n, 1))() for _ in range(3))
     check(lib().msm_segments_plan(o, k, piece, ctypes.byref(npieces), st, ct, sg, n))
     return [(st[i], ct[i], sg[i]) for i in range(n)]
+
+
+def _h2c_messages(group, msgs, offsets, msg_len, aug, aug_len, src_on_device, n=None):
+    """(n, msgs pointer or buffer, offsets array or None, msg_len, aug pointer / buffer or None, aug_len)
+    of a hash-to-curve call, checked before any device work"""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if isinstance(msgs, (list, tuple)):
+        if offsets is not None or msg_len is not None or src_on_device:
+            raise ValueError("a list of messages brings its own offsets and lives in host memory")
+        parts = [bytes(p) for p in msgs]
+        offsets = [0]
+        for p in parts:
+            offsets.append(offsets[-1] + len(p))
+        msgs = b"".join(parts)
+    if (offsets is None) == (msg_len is None):
+        raise ValueError("give exactly one of offsets and msg_len")
+    if aug_len < 0:
+        raise ValueError("aug_len must be >= 0")
+    if offsets is not None:
+        offs = [int(v) for v in offsets]
+        if not offs:
+            raise ValueError("offsets must hold n + 1 values")
+        if offs[0] < 0 or any(b < a for a, b in zip(offs, offs[1:])):
+            raise ValueError("offsets must be non-negative and non-decreasing")
+        n, need, ml = len(offs) - 1, offs[-1], 0
+        o = (ctypes.c_size_t * len(offs))(*offs)
+    else:
+        ml = int(msg_len)
+        if ml < 0:
+            raise ValueError("msg_len must be >= 0")
+        if src_on_device:
+            if n is None or n < 0:
+                raise ValueError("fixed-length messages in device memory need n")
+        else:
+            have = len(msgs)
+            if n is None:
+                if ml == 0 or have % ml:
+                    raise ValueError(f"{have} bytes of messages are no multiple of msg_len {ml}")
+                n = have // ml
+            elif n < 0:
+                raise ValueError("n must be >= 0")
+        need, o = n * ml, None
+    if aug is None:
+        aug_len = 0
+    if src_on_device:
+        return n, msgs, o, ml, aug, aug_len
+    src = _buf(msgs) if need else None
+    if need:
+        have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+        if have < need:
+            raise ValueError(f"{have} bytes of messages given, {need} needed")
+    a = None
+    if aug is not None and aug_len:
+        a = _buf(aug)
+        have = len(a) if hasattr(a, "__len__") else ctypes.sizeof(a)
+        if have < n * aug_len:
+            raise ValueError(f"{have} bytes of aug given, {n * aug_len} needed")
+    return n, src, o, ml, a, aug_len
+
+
+def ps_map_to_curve(group, u, n, *, count=2, src_on_device=False, dst=None, device=0, stream=None):
+    """n points from n * count field elements (msm_points_map): out[i] is the affine form
+    of blst_map_to_g{1,2}(u[i count], u[i count + 1] if count == 2), infinity the all-zero
+    point.  u: elements in blst's Montgomery layout, 48 G bytes each, canonical; nothing
+    is validated.  A host source is a bytes-like object, a device source (src_on_device)
+    a device pointer.  With dst=<device pointer> the points are written there, ordered on
+    `stream`, and None is returned."""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if count not in (1, 2):
+        raise ValueError("count must be 1 or 2")
+    if src_on_device:
+        src = u
+    else:
+        src = _buf(u)
+        have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+        if have < n * count * 48 * group:
+            raise ValueError(f"{have} bytes of field elements given, {n * count * 48 * group} needed")
+    if dst is not None:
+        check(lib().msm_points_map(group, device, dst, src, n, count, int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (POINT_BYTES[group] * n))()
+    check(lib().msm_points_map(group, device, out, src, n, count, int(bool(src_on_device)), 0, stream))
+    return bytes(out)
+
+
+def ps_hash_to_field(group, msgs, *, dst_tag, count=2, offsets=None, msg_len=None, n=None, aug=None, aug_len=0,
+                     src_on_device=False, dst=None, device=0, stream=None):
+    """count field elements per message (msm_hash_to_field): RFC 9380 hash_to_field over
+    expand_message_xmd with SHA-256, in blst's Montgomery layout (48 G bytes each), what
+    the reference's hash_to_field yields.  Messages, offsets, aug and dst_tag as in
+    ps_hash_to_curve."""
+    if count not in (1, 2):
+        raise ValueError("count must be 1 or 2")
+    n, src, o, ml, a, al = _h2c_messages(group, msgs, offsets, msg_len, aug, aug_len, src_on_device, n)
+    tag = bytes(dst_tag)
+    if dst is not None:
+        check(lib().msm_hash_to_field(group, device, dst, src, o, ml, a, al, n, tag, len(tag), count,
+                                      int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (48 * group * count * n))()
+    check(lib().msm_hash_to_field(group, device, out, src, o, ml, a, al, n, tag, len(tag), count,
+                                  int(bool(src_on_device)), 0, stream))
+    return bytes(out)
+
+
+def ps_hash_to_curve(group, msgs, *, dst_tag, offsets=None, msg_len=None, n=None, aug=None, aug_len=0, encode=False,
+                     src_on_device=False, dst=None, device=0, stream=None):
+    """One point per message (msm_points_hash): the affine form of blst_hash_to_g{1,2}, or
+    with encode of blst_encode_to_g{1,2}, under the domain separation tag dst_tag (host
+    bytes, any length).  msgs: a list of bytes objects, or one bytes-like object (device
+    pointer with src_on_device) cut by offsets (n + 1 non-decreasing ints) or into
+    msg_len-byte messages (n of them; n may be left out for host memory).  aug: n * aug_len bytes in the memory space of msgs, slice i
+    hashed in front of message i.  With dst=<device pointer> the points are written
+    there, ordered on `stream`, and None is returned."""
+    n, src, o, ml, a, al = _h2c_messages(group, msgs, offsets, msg_len, aug, aug_len, src_on_device, n)
+    tag = bytes(dst_tag)
+    flags = H2C_ENCODE if encode else 0
+    if dst is not None:
+        check(lib().msm_points_hash(group, device, dst, src, o, ml, a, al, n, tag, len(tag), flags,
+                                    int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (POINT_BYTES[group] * n))()
+    check(lib().msm_points_hash(group, device, out, src, o, ml, a, al, n, tag, len(tag), flags,
+                                int(bool(src_on_device)), 0, stream))
+    return bytes(out)
+
+
+def h2c_dst_prime(dst_tag):
+    """DST_prime = DST || I2OSP(len, 1) after the oversize rule (msm_h2c_dst_prime; host only)."""
+    tag = bytes(dst_tag)
+    out = (ctypes.c_uint8 * 256)()
+    n = ctypes.c_size_t(0)
+    check(lib().msm_h2c_dst_prime(out, ctypes.byref(n), tag, len(tag)))
+    return bytes(out[:n.value])
 
 
 def to_affine_levels(n):

@@ -135,6 +135,10 @@ def lib():
     L.msm_segments_piece.argtypes = [i32, sz]
     L.msm_segments_piece.restype = sz
     L.msm_segments_plan.argtypes = [vp, sz, sz, vp, vp, vp, vp, sz]
+    L.msm_points_map.argtypes = [i32, i32, vp, vp, sz, i32, i32, i32, vp]
+    L.msm_hash_to_field.argtypes = [i32, i32, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, i32, i32, vp]
+    L.msm_points_hash.argtypes = [i32, i32, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, i32, i32, vp]
+    L.msm_h2c_dst_prime.argtypes = [vp, vp, vp, sz]
     _lib = L
     return L
 

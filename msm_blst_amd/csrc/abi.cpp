@@ -20,6 +20,7 @@
 #include "decode.hpp"
 #include "encode.hpp"
 #include "engine.hpp"
+#include "hash_to_curve.hpp"
 #include "multi.hpp"
 #include "point_segments.hpp"
 #include "points_mult.hpp"
@@ -560,6 +561,74 @@ int points_segments_checked(int group, int dev, void *dst, const void *points, c
   }
 }
 
+// ---- bulk hash-to-curve (a loop over ref map_to_g{1,2}.c hash / encode / map, hash_to_field.c) ----
+// cs orders the kernels: the caller's stream when a side is device memory, else
+// the leased engine's own.
+template <int G>
+void hash_to_curve(int dev, int mode, void *dst, const void *u, const H2cMsgs &m, const H2cTemplate *tmpl, size_t n,
+                   int count, bool src_dev, bool dst_dev, hipStream_t user) {
+  DeviceGuard g(dev);
+  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+  auto eng = EnginePool<HashToCurve<G>>::get().lease(dev, G, [&] { return std::make_unique<HashToCurve<G>>(dev); });
+  const bool on_user = src_dev || dst_dev;
+  hipStream_t cs = on_user ? user : eng->stream();
+  (*eng)->run(cs, mode, u, m, tmpl, dst, n, count, src_dev, dst_dev);
+  // the legacy default stream gives the caller nothing to wait on: finish here
+  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+int hash_to_curve_checked(int group, int dev, int mode, void *dst, const void *u, const void *msgs,
+                          const size_t *offsets, size_t msg_len, const void *aug, size_t aug_len, size_t n,
+                          const byte *DST, size_t DST_len, int count, bool src_dev, bool dst_dev, hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (count != 1 && count != 2) return fail(MSM_E_ARG, "count must be 1 or 2");
+  if (n == 0) return MSM_OK;  // nothing touched
+  if (!dst) return fail(MSM_E_ARG, "null dst");
+  if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
+  const size_t elem = (size_t)48 * group;
+  const size_t out_bytes = n * (mode == H2C_FIELD ? count * elem : 2 * elem);
+  H2cMsgs m;
+  H2cTemplate tmpl;
+  if (mode == H2C_MAP) {
+    if (!u) return fail(MSM_E_ARG, "null u");
+    if (src_dev && ((uintptr_t)u & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
+    if (!src_dev && !dst_dev && ranges_overlap(u, n * count * elem, dst, out_bytes))
+      return fail(MSM_E_ARG, "source and destination overlap");
+  } else {
+    if (DST_len && !DST) return fail(MSM_E_ARG, "null DST");
+    if (offsets && !seg_offsets_ok(offsets, n)) return fail(MSM_E_ARG, "offsets decrease");
+    if (offsets)  // the kernel counts the bytes of a message in 32 bits
+      for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] - offsets[i] > ((size_t)1 << 30)) return fail(MSM_E_ARG, "a message longer than 2^30 bytes");
+    const size_t first = offsets ? offsets[0] : 0, last = offsets ? offsets[n] : n * msg_len;
+    if (!offsets && msg_len > ((size_t)1 << 30)) return fail(MSM_E_ARG, "msg_len out of range");
+    if (last > first && !msgs) return fail(MSM_E_ARG, "null msgs");
+    if (aug_len > ((size_t)1 << 30)) return fail(MSM_E_ARG, "aug_len out of range");
+    if (!src_dev && !dst_dev &&
+        ((last > first && ranges_overlap((const uint8_t *)msgs + first, last - first, dst, out_bytes)) ||
+         (aug && aug_len && ranges_overlap(aug, n * aug_len, dst, out_bytes))))
+      return fail(MSM_E_ARG, "source and destination overlap");
+    m.msgs = (const uint8_t *)msgs;
+    m.offsets = offsets;
+    m.msg_len = msg_len;
+    m.aug = aug_len ? (const uint8_t *)aug : nullptr;
+    m.aug_len = aug ? aug_len : 0;
+    h2c_make_template(tmpl, DST, DST_len, (unsigned)(64 * count * group));
+  }
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    if (group == 1) hash_to_curve<1>(dev, mode, dst, u, m, &tmpl, n, count, src_dev, dst_dev, user);
+    else hash_to_curve<2>(dev, mode, dst, u, m, &tmpl, n, count, src_dev, dst_dev, user);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (!dst_dev) memset(dst, 0, out_bytes);  // never half written
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   size_t w = 0;
   while (n >>= 1) ++w;
@@ -964,6 +1033,35 @@ int msm_segments_plan(const size_t *offsets, size_t nsegments, size_t piece, siz
                                    ++w;
                                  })
                        : 0;
+  return MSM_OK;
+}
+
+int msm_points_map(int group, int device, void *dst_affine, const void *u, size_t npoints, int count,
+                   int src_on_device, int dst_on_device, void *hip_stream) {
+  return hash_to_curve_checked(group, device, H2C_MAP, dst_affine, u, nullptr, nullptr, 0, nullptr, 0, npoints, nullptr,
+                               0, count, src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_hash_to_field(int group, int device, void *dst_elems, const void *msgs, const size_t *offsets, size_t msg_len,
+                      const void *aug, size_t aug_len, size_t npoints, const byte *DST, size_t DST_len, int count,
+                      int src_on_device, int dst_on_device, void *hip_stream) {
+  return hash_to_curve_checked(group, device, H2C_FIELD, dst_elems, nullptr, msgs, offsets, msg_len, aug, aug_len,
+                               npoints, DST, DST_len, count, src_on_device != 0, dst_on_device != 0,
+                               (hipStream_t)hip_stream);
+}
+
+int msm_points_hash(int group, int device, void *dst_affine, const void *msgs, const size_t *offsets, size_t msg_len,
+                    const void *aug, size_t aug_len, size_t npoints, const byte *DST, size_t DST_len, int flags,
+                    int src_on_device, int dst_on_device, void *hip_stream) {
+  if (flags & ~MSM_H2C_ENCODE) return fail(MSM_E_ARG, "unknown flag bits");
+  return hash_to_curve_checked(group, device, H2C_HASH, dst_affine, nullptr, msgs, offsets, msg_len, aug, aug_len,
+                               npoints, DST, DST_len, (flags & MSM_H2C_ENCODE) ? 1 : 2, src_on_device != 0,
+                               dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_h2c_dst_prime(byte *out, size_t *out_len, const byte *DST, size_t DST_len) {
+  if (!out || !out_len || (DST_len && !DST)) return fail(MSM_E_ARG, "null out / out_len / DST");
+  *out_len = h2c_dst_prime(out, DST, DST_len);
   return MSM_OK;
 }
 
