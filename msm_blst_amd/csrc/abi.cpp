@@ -297,25 +297,44 @@ void wbits_mult(void *ret, const void *table, size_t wbits, size_t n, const byte
   memcpy(ret, &out, sizeof out);
 }
 
-// ---- bulk Jacobian -> affine (ref multi_scalar.c:17-62) ----
-// runs: the host source as runs of adjacent points (ptr_walk.hpp), or empty
-// with src_dev set.  cs orders the kernels: the caller's stream when a side is
-// device memory, else the leased engine's own.
-template <int G>
-void points_to_affine(int dev, void *dst, const void *src_dev_ptr,
-                      const std::vector<typename ToAffine<G>::Run> &runs, size_t n, bool src_dev, bool dst_dev,
-                      hipStream_t user) {
+// ---- the bulk point operations (engines on the chunk pipe, chunk_pipe.hpp) ----
+// What their calls share: run(engine, cs) on a leased engine E (pool key
+// `group`) of device `dev`.  cs orders the kernels: the caller's stream when a
+// side is device memory, else the leased engine's own.
+template <class E, class Run>
+void bulk_run(int dev, int group, bool src_dev, bool dst_dev, hipStream_t user, Run run) {
   DeviceGuard g(dev);
   // work queued earlier on the caller's stream may still be writing the source:
   // device sources are read by kernels ordered on that stream; host sources are
   // read by this thread, so the stream is drained first
   if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-  auto eng = EnginePool<ToAffine<G>>::get().lease(dev, G, [&] { return std::make_unique<ToAffine<G>>(dev); });
+  auto eng = EnginePool<E>::get().lease(dev, group, [&] { return std::make_unique<E>(dev); });
   const bool on_user = src_dev || dst_dev;
   hipStream_t cs = on_user ? user : eng->stream();
-  (*eng)->run(cs, src_dev_ptr, runs, dst, n, src_dev, dst_dev);
+  run(**eng, cs);
   // the legacy default stream gives the caller nothing to wait on: finish here
   if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+}
+
+// the result of a bulk call whose every output is the point at infinity, in the place of bulk_run
+void zero_fill(int dev, void *dst, size_t bytes, bool src_dev, bool dst_dev, hipStream_t user) {
+  DeviceGuard g(dev);
+  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));  // (as bulk_run does)
+  if (dst_dev) MSM_HIP_CHECK(hipMemsetAsync(dst, 0, bytes, user));
+  else memset(dst, 0, bytes);
+  if (dst_dev && !user) MSM_HIP_CHECK(hipStreamSynchronize(user));
+}
+
+// ---- bulk Jacobian -> affine (ref multi_scalar.c:17-62) ----
+// runs: the host source as runs of adjacent points (ptr_walk.hpp), or empty
+// with src_dev set.
+template <int G>
+void points_to_affine(int dev, void *dst, const void *src_dev_ptr,
+                      const std::vector<typename ToAffine<G>::Run> &runs, size_t n, bool src_dev, bool dst_dev,
+                      hipStream_t user) {
+  bulk_run<ToAffine<G>>(dev, G, src_dev, dst_dev, user, [&](ToAffine<G> &e, hipStream_t cs) {
+    e.run(cs, src_dev_ptr, runs, dst, n, src_dev, dst_dev);
+  });
 }
 
 constexpr int kCurrentDevice = -0x7fffffff;  // the blst-style calls: hipGetDevice
@@ -355,20 +374,13 @@ int points_to_affine_checked(int dev, void *dst, const void *src_flat, const voi
 }
 
 // ---- bulk point decoding (ref e1.c:236-351, e2.c:279-410, map_to_g{1,2}.c in_g{1,2}) ----
-// status: n host bytes or NULL.  cs orders the kernels: the caller's stream when
-// a side is device memory, else the leased engine's own.
+// status: n host bytes or NULL.
 template <int G>
 void points_decode(int dev, void *dst, uint8_t *status, const void *src, size_t n, bool serialized, bool check_group,
                    bool src_dev, bool dst_dev, hipStream_t user) {
-  DeviceGuard g(dev);
-  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
-  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-  auto eng = EnginePool<Decode<G>>::get().lease(dev, G, [&] { return std::make_unique<Decode<G>>(dev); });
-  const bool on_user = src_dev || dst_dev;
-  hipStream_t cs = on_user ? user : eng->stream();
-  (*eng)->run(cs, src, dst, status, n, serialized, check_group, src_dev, dst_dev);
-  // the legacy default stream gives the caller nothing to wait on: finish here
-  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+  bulk_run<Decode<G>>(dev, G, src_dev, dst_dev, user, [&](Decode<G> &e, hipStream_t cs) {
+    e.run(cs, src, dst, status, n, serialized, check_group, src_dev, dst_dev);
+  });
 }
 
 int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t *nbad, const void *src, size_t n,
@@ -410,20 +422,12 @@ int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t
 }
 
 // ---- bulk point encoding (a loop over ref e1.c:139-234 and the e2.c twins) ----
-// cs orders the kernels: the caller's stream when a side is device memory, else
-// the leased engine's own.
 template <int G>
 void points_encode(int dev, void *dst, const void *src, size_t n, bool jacobian, bool serialized, bool src_dev,
                    bool dst_dev, hipStream_t user) {
-  DeviceGuard g(dev);
-  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
-  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-  auto eng = EnginePool<Encode<G>>::get().lease(dev, G, [&] { return std::make_unique<Encode<G>>(dev); });
-  const bool on_user = src_dev || dst_dev;
-  hipStream_t cs = on_user ? user : eng->stream();
-  (*eng)->run(cs, src, dst, n, jacobian, serialized, src_dev, dst_dev);
-  // the legacy default stream gives the caller nothing to wait on: finish here
-  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+  bulk_run<Encode<G>>(dev, G, src_dev, dst_dev, user, [&](Encode<G> &e, hipStream_t cs) {
+    e.run(cs, src, dst, n, jacobian, serialized, src_dev, dst_dev);
+  });
 }
 
 int points_encode_checked(int group, int dev, void *dst, const void *src, size_t n, int src_form, int encoding,
@@ -454,26 +458,13 @@ int points_encode_checked(int group, int dev, void *dst, const void *src, size_t
 }
 
 // ---- bulk scalar multiplication (a loop over ref e1.c:505-533 blst_p1_mult, e2.c, ec_mult.h) ----
-// cs orders the kernels: the caller's stream when a side is device memory, else
-// the leased engine's own.
 template <int G>
 void points_mult(int dev, void *dst, const void *points, const uint8_t *scalars, size_t n, int nbits, size_t stride,
                  bool one_point, bool src_dev, bool dst_dev, hipStream_t user) {
-  DeviceGuard g(dev);
-  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
-  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-  if (nbits == 0) {  // every scalar is zero
-    if (dst_dev) MSM_HIP_CHECK(hipMemsetAsync(dst, 0, n * 96 * G, user));
-    else memset(dst, 0, n * 96 * G);
-    if (dst_dev && !user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-    return;
-  }
-  auto eng = EnginePool<PointsMult<G>>::get().lease(dev, G, [&] { return std::make_unique<PointsMult<G>>(dev); });
-  const bool on_user = src_dev || dst_dev;
-  hipStream_t cs = on_user ? user : eng->stream();
-  (*eng)->run(cs, points, scalars, dst, n, nbits, stride, one_point, src_dev, dst_dev);
-  // the legacy default stream gives the caller nothing to wait on: finish here
-  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+  if (nbits == 0) return zero_fill(dev, dst, n * 96 * G, src_dev, dst_dev, user);  // every scalar is zero
+  bulk_run<PointsMult<G>>(dev, G, src_dev, dst_dev, user, [&](PointsMult<G> &e, hipStream_t cs) {
+    e.run(cs, points, scalars, dst, n, nbits, stride, one_point, src_dev, dst_dev);
+  });
 }
 
 int points_mult_checked(int group, int dev, void *dst, const void *points, const byte *scalars, size_t n, size_t nbits,
@@ -504,26 +495,14 @@ int points_mult_checked(int group, int dev, void *dst, const void *points, const
 }
 
 // ---- segmented sums and MSMs (a loop over ref multi_scalar.c:581-607 / bulk_addition.c:145-164 per point set) ----
-// cs orders the kernels: the caller's stream when a side is device memory, else
-// the leased engine's own.
 template <int G>
 void points_segments(int dev, void *dst, const void *points, const uint8_t *scalars, const size_t *offsets, size_t k,
                      int nbits, size_t stride, bool src_dev, bool dst_dev, hipStream_t user) {
-  DeviceGuard g(dev);
-  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
-  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-  if ((scalars && nbits == 0) || offsets[k] == offsets[0]) {  // every scalar is zero, or every segment is empty
-    if (dst_dev) MSM_HIP_CHECK(hipMemsetAsync(dst, 0, k * 96 * G, user));
-    else memset(dst, 0, k * 96 * G);
-    if (dst_dev && !user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-    return;
-  }
-  auto eng = EnginePool<PointSegments<G>>::get().lease(dev, G, [&] { return std::make_unique<PointSegments<G>>(dev); });
-  const bool on_user = src_dev || dst_dev;
-  hipStream_t cs = on_user ? user : eng->stream();
-  (*eng)->run(cs, points, scalars, offsets, k, dst, nbits, stride, src_dev, dst_dev);
-  // the legacy default stream gives the caller nothing to wait on: finish here
-  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+  if ((scalars && nbits == 0) || offsets[k] == offsets[0])  // every scalar is zero, or every segment is empty
+    return zero_fill(dev, dst, k * 96 * G, src_dev, dst_dev, user);
+  bulk_run<PointSegments<G>>(dev, G, src_dev, dst_dev, user, [&](PointSegments<G> &e, hipStream_t cs) {
+    e.run(cs, points, scalars, offsets, k, dst, nbits, stride, src_dev, dst_dev);
+  });
 }
 
 int points_segments_checked(int group, int dev, void *dst, const void *points, const byte *scalars,
@@ -562,20 +541,12 @@ int points_segments_checked(int group, int dev, void *dst, const void *points, c
 }
 
 // ---- bulk hash-to-curve (a loop over ref map_to_g{1,2}.c hash / encode / map, hash_to_field.c) ----
-// cs orders the kernels: the caller's stream when a side is device memory, else
-// the leased engine's own.
 template <int G>
 void hash_to_curve(int dev, int mode, void *dst, const void *u, const H2cMsgs &m, const H2cTemplate *tmpl, size_t n,
                    int count, bool src_dev, bool dst_dev, hipStream_t user) {
-  DeviceGuard g(dev);
-  // a host source is read by this thread: work queued earlier on the caller's stream may still be writing it
-  if (!src_dev && user) MSM_HIP_CHECK(hipStreamSynchronize(user));
-  auto eng = EnginePool<HashToCurve<G>>::get().lease(dev, G, [&] { return std::make_unique<HashToCurve<G>>(dev); });
-  const bool on_user = src_dev || dst_dev;
-  hipStream_t cs = on_user ? user : eng->stream();
-  (*eng)->run(cs, mode, u, m, tmpl, dst, n, count, src_dev, dst_dev);
-  // the legacy default stream gives the caller nothing to wait on: finish here
-  if (on_user && !user && dst_dev) MSM_HIP_CHECK(hipStreamSynchronize(cs));
+  bulk_run<HashToCurve<G>>(dev, G, src_dev, dst_dev, user, [&](HashToCurve<G> &e, hipStream_t cs) {
+    e.run(cs, mode, u, m, tmpl, dst, n, count, src_dev, dst_dev);
+  });
 }
 
 int hash_to_curve_checked(int group, int dev, int mode, void *dst, const void *u, const void *msgs,

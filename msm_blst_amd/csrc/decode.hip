@@ -198,55 +198,6 @@ static __global__ void __launch_bounds__(128, 2) k_decode_group(uint64_t *out, u
   }
 }
 
-template <int G>
-Decode<G>::Decode(int device) : dev_(device) {
-  DeviceGuard g(dev_);
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
-  }
-  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
-}
-
-template <int G>
-Decode<G>::~Decode() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(dev_);
-  // queued work may still read the staging and status buffers
-  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
-  if (h2d_) (void)hipStreamSynchronize(h2d_);
-  if (d2h_) (void)hipStreamSynchronize(d2h_);
-  for (int i = 0; i < 2; ++i) {
-    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
-    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
-    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
-    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
-    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
-    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
-    if (pin_st_[i]) (void)hipHostFree(pin_st_[i]);
-  }
-  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
-  if (h2d_) (void)hipStreamDestroy(h2d_);
-  if (d2h_) (void)hipStreamDestroy(d2h_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-template <int G>
-void Decode<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
-  if (bytes <= have) return;
-  for (int i = 0; i < 2; ++i) {
-    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
-    slots[i] = nullptr;
-  }
-  have = 0;
-  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
-  have = bytes;
-}
-
 // one chunk, device to device
 template <int G>
 void Decode<G>::kernels(hipStream_t s, const void *d_src, void *d_dst, uint8_t *d_status, size_t n, bool serialized,
@@ -276,27 +227,14 @@ void Decode<G>::run(hipStream_t cs, const void *src, void *dst, uint8_t *status,
   const bool out_host = !dst_dev || status;  // something comes back per chunk
   dst_[0].ensure(C);
   dst_[1].ensure(C);
-  if (!src_dev) {
-    ensure_pinned(pin_in_, pin_in_bytes_, C * ENC);
-    din_[0].ensure(C * ENC);
-    din_[1].ensure(C * ENC);
-  }
-  if (!dst_dev) {
-    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
-    dout_[0].ensure(C * AFF);
-    dout_[1].ensure(C * AFF);
-  }
-  if (status) ensure_pinned(pin_st_, pin_st_bytes_, C);
-  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the status buffers of the previous call
-  struct Pending {
-    int slot;
-    size_t off, cnt;
-  } prev{0, 0, 0};
-  auto drain = [&](const Pending &p) {
-    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
-    if (!dst_dev) memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
-    if (status) memcpy(status + p.off, pin_st_[p.slot], p.cnt);
-  };
+  if (!src_dev) in_.ensure(C * ENC);
+  if (!dst_dev) out_.ensure(C * AFF);
+  if (status) st_.ensure(C, false);
+  pipe_.begin(cs);  // the status buffers of the previous call
+  auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {
+    if (!dst_dev) memcpy(static_cast<uint8_t *>(dst) + off * AFF, out_.pin[slot], cnt * AFF);
+    if (status) memcpy(status + off, st_.pin[slot], cnt);
+  });
   size_t k = 0;
   for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
     const size_t cnt = std::min(C, n - c0);
@@ -304,32 +242,29 @@ void Decode<G>::run(hipStream_t cs, const void *src, void *dst, uint8_t *status,
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
-      memcpy(pin_in_[slot], static_cast<const uint8_t *>(src) + c0 * ENC, cnt * ENC);
-      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
-      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], cnt * ENC, hipMemcpyHostToDevice, h2d_));
-      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
-      d_src = din_[slot].p;
+      pipe_.in_open(slot);
+      memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + c0 * ENC, cnt * ENC);
+      pipe_.in_gate(slot);
+      pipe_.in_copy(slot, in_, cnt * ENC);
+      pipe_.in_close(cs, slot);
+      d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src) + c0 * ENC;
     }
-    if (out_host) MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_ / dst_[slot]
-    d_dst = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * AFF) : dout_[slot].p;
+    if (out_host) pipe_.out_open(cs, slot);  // (guards dst_[slot] as well as the output slot)
+    d_dst = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * AFF) : out_.dev[slot].p;
     kernels(cs, d_src, d_dst, dst_[slot].as<uint8_t>(), cnt, serialized, check_group);
-    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    pipe_.computed(cs, slot);
     if (out_host) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
-      if (!dst_dev)
-        MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * AFF, hipMemcpyDeviceToHost, d2h_));
-      if (status) MSM_HIP_CHECK(hipMemcpyAsync(pin_st_[slot], dst_[slot].p, cnt, hipMemcpyDeviceToHost, d2h_));
-      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
-      if (k) drain(prev);  // chunk k - 1, while chunk k runs
-      prev = Pending{slot, c0, cnt};
+      pipe_.out_gate(slot);
+      if (!dst_dev) pipe_.out_copy(slot, out_, cnt * AFF);
+      if (status) pipe_.out_copy(st_.pin[slot], dst_[slot].p, cnt);
+      pipe_.out_close(slot);
+      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
     }
   }
-  if (out_host) drain(prev);
-  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+  pend.flush();
+  pipe_.finish(cs);
 }
 
 template class Decode<MSM_GROUP>;

@@ -6,9 +6,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
-#include "engine.hpp"
+#include "chunk_pipe.hpp"
 
 namespace msm {
 
@@ -16,24 +15,18 @@ constexpr size_t DEC_CHUNK_DEFAULT = (size_t)1 << 18;
 
 // entries per chunk: MSM_DECODE_CHUNK=<entries> overrides the default, read at each call
 inline size_t dec_chunk() {
-  const char *e = getenv("MSM_DECODE_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v > 0) return (size_t)v;
-  }
-  return DEC_CHUNK_DEFAULT;
+  const size_t e = env_size("MSM_DECODE_CHUNK");
+  return e ? e : DEC_CHUNK_DEFAULT;
 }
 
-// One engine: a status buffer per slot, and for host memory two pinned + two
-// device staging buffers per direction with their own copy streams.
+// One engine: a status buffer per slot, and for host memory a staging lane per
+// direction and a pinned lane for the status bytes on the shared chunk pipe
+// (chunk_pipe.hpp).
 template <int G>
 class Decode {
  public:
   static constexpr size_t AFF = 96 * G, COMP = 48 * G;
-  explicit Decode(int device);
-  ~Decode();
-  Decode(const Decode &) = delete;
-  Decode &operator=(const Decode &) = delete;
+  explicit Decode(int device) : dev_(device), pipe_(device) {}
   // n entries of COMP (compressed) or 2 COMP (serialized) bytes at src -> n
   // affine points at dst (host or device, flat) and, when status is not NULL,
   // n status bytes in host memory.  `cs` orders the kernels (the caller's
@@ -42,20 +35,14 @@ class Decode {
   // with dst (host) and status written.
   void run(hipStream_t cs, const void *src, void *dst, uint8_t *status, size_t n, bool serialized, bool check_group,
            bool src_dev, bool dst_dev);
-  size_t device_bytes() const {
-    return din_[0].bytes + din_[1].bytes + dout_[0].bytes + dout_[1].bytes + dst_[0].bytes + dst_[1].bytes;
-  }
+  size_t device_bytes() const { return in_.device_bytes() + out_.device_bytes() + dst_[0].bytes + dst_[1].bytes; }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf din_[2], dout_[2], dst_[2];  // staged input, staged output, status bytes
-  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr}, *pin_st_[2] = {nullptr, nullptr};
-  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0, pin_st_bytes_ = 0;
-  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
-  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (the status buffers are reused)
-  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  DevBuf dst_[2];        // status bytes of a slot
+  Stage in_, out_, st_;  // st_: the status bytes' pinned slots (they come down from dst_)
+  ChunkPipe pipe_;       // (last: it waits for the queued work before the buffers go)
   void kernels(hipStream_t s, const void *d_src, void *d_dst, uint8_t *d_status, size_t n, bool serialized,
                bool check_group);
 };

@@ -53,54 +53,6 @@ static __global__ void __launch_bounds__(128)
   enc_entry<G, SER>(dst + t * (SER ? 96 : 48) * G, x, y, nz == 0, comp);
 }
 
-template <int G>
-Encode<G>::Encode(int device) : dev_(device) {
-  DeviceGuard g(dev_);
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
-  }
-  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
-}
-
-template <int G>
-Encode<G>::~Encode() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(dev_);
-  // queued work may still read the staging and level buffers
-  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
-  if (h2d_) (void)hipStreamSynchronize(h2d_);
-  if (d2h_) (void)hipStreamSynchronize(d2h_);
-  for (int i = 0; i < 2; ++i) {
-    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
-    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
-    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
-    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
-    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
-    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
-  }
-  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
-  if (h2d_) (void)hipStreamDestroy(h2d_);
-  if (d2h_) (void)hipStreamDestroy(d2h_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-template <int G>
-void Encode<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
-  if (bytes <= have) return;
-  for (int i = 0; i < 2; ++i) {
-    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
-    slots[i] = nullptr;
-  }
-  have = 0;
-  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
-  have = bytes;
-}
-
 // one chunk, device to device: n <= the chunk the level buffer was sized for
 template <int G>
 void Encode<G>::kernels(hipStream_t s, const void *d_src, void *d_dst, size_t n, bool jacobian, bool serialized) {
@@ -127,25 +79,12 @@ void Encode<G>::run(hipStream_t cs, const void *src, void *dst, size_t n, bool j
   const size_t PT = jacobian ? JAC : AFF, ENC = serialized ? 2 * COMP : COMP;
   const size_t C = std::min(n, enc_chunk());
   if (jacobian) lv_.ensure(ta_level_elems(C) * ELEM);
-  if (!src_dev) {
-    ensure_pinned(pin_in_, pin_in_bytes_, C * PT);
-    din_[0].ensure(C * PT);
-    din_[1].ensure(C * PT);
-  }
-  if (!dst_dev) {
-    ensure_pinned(pin_out_, pin_out_bytes_, C * ENC);
-    dout_[0].ensure(C * ENC);
-    dout_[1].ensure(C * ENC);
-  }
-  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the level buffer of the previous call
-  struct Pending {
-    int slot;
-    size_t off, cnt;
-  } prev{0, 0, 0};
-  auto drain = [&](const Pending &p) {
-    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
-    memcpy(static_cast<uint8_t *>(dst) + p.off * ENC, pin_out_[p.slot], p.cnt * ENC);
-  };
+  if (!src_dev) in_.ensure(C * PT);
+  if (!dst_dev) out_.ensure(C * ENC);
+  pipe_.begin(cs);  // the level buffer of the previous call
+  auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {
+    memcpy(static_cast<uint8_t *>(dst) + off * ENC, out_.pin[slot], cnt * ENC);
+  });
   size_t k = 0;
   for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
     const size_t cnt = std::min(C, n - c0);
@@ -153,34 +92,32 @@ void Encode<G>::run(hipStream_t cs, const void *src, void *dst, size_t n, bool j
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
-      memcpy(pin_in_[slot], static_cast<const uint8_t *>(src) + c0 * PT, cnt * PT);
-      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
-      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], cnt * PT, hipMemcpyHostToDevice, h2d_));
-      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
-      d_src = din_[slot].p;
+      pipe_.in_open(slot);
+      memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + c0 * PT, cnt * PT);
+      pipe_.in_gate(slot);
+      pipe_.in_copy(slot, in_, cnt * PT);
+      pipe_.in_close(cs, slot);
+      d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src) + c0 * PT;
     }
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
-      d_dst = dout_[slot].p;
+      pipe_.out_open(cs, slot);
+      d_dst = out_.dev[slot].p;
     } else {
       d_dst = static_cast<uint8_t *>(dst) + c0 * ENC;
     }
     kernels(cs, d_src, d_dst, cnt, jacobian, serialized);
-    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    pipe_.computed(cs, slot);
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
-      MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * ENC, hipMemcpyDeviceToHost, d2h_));
-      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
-      if (k) drain(prev);  // chunk k - 1, while chunk k runs
-      prev = Pending{slot, c0, cnt};
+      pipe_.out_gate(slot);
+      pipe_.out_copy(slot, out_, cnt * ENC);
+      pipe_.out_close(slot);
+      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
     }
   }
-  if (!dst_dev) drain(prev);
-  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+  pend.flush();
+  pipe_.finish(cs);
 }
 
 template class Encode<MSM_GROUP>;

@@ -6,9 +6,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
-#include "engine.hpp"
+#include "chunk_pipe.hpp"
 
 namespace msm {
 
@@ -16,25 +15,18 @@ constexpr size_t ENC_CHUNK_DEFAULT = (size_t)1 << 18;
 
 // points per chunk: MSM_ENCODE_CHUNK=<points> overrides the default, read at each call
 inline size_t enc_chunk() {
-  const char *e = getenv("MSM_ENCODE_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v > 0) return (size_t)v;
-  }
-  return ENC_CHUNK_DEFAULT;
+  const size_t e = env_size("MSM_ENCODE_CHUNK");
+  return e ? e : ENC_CHUNK_DEFAULT;
 }
 
 // One engine: the level buffer of the inversion tree (Jacobian sources,
-// to_affine.hpp), and for host memory two pinned + two device staging buffers
-// per direction with their own copy streams.
+// to_affine.hpp), and for host memory a staging lane per direction on the
+// shared chunk pipe (chunk_pipe.hpp).
 template <int G>
 class Encode {
  public:
   static constexpr size_t AFF = 96 * G, JAC = 144 * G, COMP = 48 * G, ELEM = 56 * G;
-  explicit Encode(int device);
-  ~Encode();
-  Encode(const Encode &) = delete;
-  Encode &operator=(const Encode &) = delete;
+  explicit Encode(int device) : dev_(device), pipe_(device) {}
   // n affine points (AFF bytes) or Jacobians (JAC bytes, `jacobian`) at src -> n
   // entries of COMP (compressed) or 2 COMP (serialized) bytes at dst; each side
   // flat, host or device.  `cs` orders the kernels (the caller's stream when a
@@ -42,18 +34,14 @@ class Encode {
   // the work queued on cs; host destination: returns with the data in dst.
   void run(hipStream_t cs, const void *src, void *dst, size_t n, bool jacobian, bool serialized, bool src_dev,
            bool dst_dev);
-  size_t device_bytes() const { return lv_.bytes + din_[0].bytes + din_[1].bytes + dout_[0].bytes + dout_[1].bytes; }
+  size_t device_bytes() const { return lv_.bytes + in_.device_bytes() + out_.device_bytes(); }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf lv_, din_[2], dout_[2];
-  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr};
-  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0;
-  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
-  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (the level buffer is reused)
-  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  DevBuf lv_;
+  Stage in_, out_;
+  ChunkPipe pipe_;  // (last: it waits for the queued work before the buffers go)
   void kernels(hipStream_t s, const void *d_src, void *d_dst, size_t n, bool jacobian, bool serialized);
 };
 

@@ -519,54 +519,6 @@ static __global__ void __launch_bounds__(128)
 }
 
 // -------------------------------------------------------------- engine ----
-template <int G>
-HashToCurve<G>::HashToCurve(int device) : dev_(device) {
-  DeviceGuard g(dev_);
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
-  }
-  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
-}
-
-template <int G>
-HashToCurve<G>::~HashToCurve() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(dev_);
-  // queued work may still read the staging buffers and the template
-  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
-  if (h2d_) (void)hipStreamSynchronize(h2d_);
-  if (d2h_) (void)hipStreamSynchronize(d2h_);
-  for (int i = 0; i < 2; ++i) {
-    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
-    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
-    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
-    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
-    for (void *p : {pin_in_[i], pin_aug_[i], pin_off_[i], pin_out_[i], pin_tp_[i]})
-      if (p) (void)hipHostFree(p);
-  }
-  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
-  if (h2d_) (void)hipStreamDestroy(h2d_);
-  if (d2h_) (void)hipStreamDestroy(d2h_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-template <int G>
-void HashToCurve<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
-  if (bytes <= have) return;
-  for (int i = 0; i < 2; ++i) {
-    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
-    slots[i] = nullptr;
-  }
-  have = 0;
-  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
-  have = bytes;
-}
-
 // one chunk of the map, device to device: n * count elements at d_u -> n affine points at d_dst
 template <int G>
 void HashToCurve<G>::map_kernels(hipStream_t s, const void *d_u, void *d_dst, size_t n, int count) {
@@ -595,7 +547,7 @@ void HashToCurve<G>::run(hipStream_t cs, int mode, const void *u, const H2cMsgs 
   const bool stage = !src_dev || offs_up;
   auto msg_begin = [&](size_t i) { return m.offsets ? m.offsets[i] : i * m.msg_len; };
   // the previous call has finished: its chunk buffers and its template are free
-  MSM_HIP_CHECK(hipEventSynchronize(ev_busy_));
+  pipe_.begin_on_host();
   if (mapping) {
     e_.ensure(C * count * XYZZ);
     x_.ensure(C * XYZZ);
@@ -608,35 +560,20 @@ void HashToCurve<G>::run(hipStream_t cs, int mode, const void *u, const H2cMsgs 
     if (!hashing) in = C * UB;
     else
       for (size_t c0 = 0; c0 < n; c0 += C) in = std::max(in, msg_begin(std::min(n, c0 + C)) - msg_begin(c0));
-    ensure_pinned(pin_in_, pin_in_bytes_, in);
-    for (int i = 0; i < 2; ++i) din_[i].ensure(in);
-    if (hashing && m.aug && m.aug_len) {
-      ensure_pinned(pin_aug_, pin_aug_bytes_, C * m.aug_len);
-      for (int i = 0; i < 2; ++i) daug_[i].ensure(C * m.aug_len);
-    }
+    in_.ensure(in);
+    if (hashing && m.aug && m.aug_len) aug_.ensure(C * m.aug_len);
   }
-  if (offs_up) {
-    ensure_pinned(pin_off_, pin_off_bytes_, (C + 1) * sizeof(size_t));
-    for (int i = 0; i < 2; ++i) doff_[i].ensure((C + 1) * sizeof(size_t));
-  }
-  if (!dst_dev) {
-    ensure_pinned(pin_out_, pin_out_bytes_, C * OUT);
-    for (int i = 0; i < 2; ++i) dout_[i].ensure(C * OUT);
-  }
+  if (offs_up) off_.ensure((C + 1) * sizeof(size_t));
+  if (!dst_dev) out_.ensure(C * OUT);
   if (hashing) {
     tp_.ensure(sizeof(H2cTemplate));
-    ensure_pinned(pin_tp_, pin_tp_bytes_, sizeof(H2cTemplate));
-    memcpy(pin_tp_[0], tmpl, sizeof(H2cTemplate));
-    MSM_HIP_CHECK(hipMemcpyAsync(tp_.p, pin_tp_[0], sizeof(H2cTemplate), hipMemcpyHostToDevice, cs));
+    tpl_.ensure(sizeof(H2cTemplate), false);
+    memcpy(tpl_.pin[0], tmpl, sizeof(H2cTemplate));
+    MSM_HIP_CHECK(hipMemcpyAsync(tp_.p, tpl_.pin[0], sizeof(H2cTemplate), hipMemcpyHostToDevice, cs));
   }
-  struct Pending {
-    int slot;
-    size_t off, cnt;
-  } prev{0, 0, 0};
-  auto drain = [&](const Pending &p) {
-    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
-    memcpy(static_cast<uint8_t *>(dst) + p.off * OUT, pin_out_[p.slot], p.cnt * OUT);
-  };
+  auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {
+    memcpy(static_cast<uint8_t *>(dst) + off * OUT, out_.pin[slot], cnt * OUT);
+  });
   const bool has_aug = hashing && m.aug && m.aug_len;
   size_t k = 0;
   for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
@@ -644,35 +581,31 @@ void HashToCurve<G>::run(hipStream_t cs, int mode, const void *u, const H2cMsgs 
     const int slot = (int)(k & 1);
     const size_t b0 = hashing ? msg_begin(c0) : 0, b1 = hashing ? msg_begin(c0 + cnt) : 0;
     if (stage) {
-      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slots
+      pipe_.in_open(slot);  // (one event for the three upload lanes)
       if (!src_dev) {
-        if (!hashing) memcpy(pin_in_[slot], static_cast<const uint8_t *>(u) + c0 * UB, cnt * UB);
-        else if (b1 > b0) memcpy(pin_in_[slot], m.msgs + b0, b1 - b0);
-        if (has_aug) memcpy(pin_aug_[slot], m.aug + c0 * m.aug_len, cnt * m.aug_len);
+        if (!hashing) memcpy(in_.pin[slot], static_cast<const uint8_t *>(u) + c0 * UB, cnt * UB);
+        else if (b1 > b0) memcpy(in_.pin[slot], m.msgs + b0, b1 - b0);
+        if (has_aug) memcpy(aug_.pin[slot], m.aug + c0 * m.aug_len, cnt * m.aug_len);
       }
-      if (offs_up) memcpy(pin_off_[slot], m.offsets + c0, (cnt + 1) * sizeof(size_t));
-      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read the device slots
+      if (offs_up) memcpy(off_.pin[slot], m.offsets + c0, (cnt + 1) * sizeof(size_t));
+      pipe_.in_gate(slot);
       if (!src_dev) {
         const size_t in = hashing ? b1 - b0 : cnt * UB;
-        if (in) MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], in, hipMemcpyHostToDevice, h2d_));
-        if (has_aug)
-          MSM_HIP_CHECK(hipMemcpyAsync(daug_[slot].p, pin_aug_[slot], cnt * m.aug_len, hipMemcpyHostToDevice, h2d_));
+        if (in) pipe_.in_copy(slot, in_, in);
+        if (has_aug) pipe_.in_copy(slot, aug_, cnt * m.aug_len);
       }
-      if (offs_up)
-        MSM_HIP_CHECK(
-            hipMemcpyAsync(doff_[slot].p, pin_off_[slot], (cnt + 1) * sizeof(size_t), hipMemcpyHostToDevice, h2d_));
-      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
+      if (offs_up) pipe_.in_copy(slot, off_, (cnt + 1) * sizeof(size_t));
+      pipe_.in_close(cs, slot);
     }
-    if (!dst_dev) MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
-    void *d_out = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * OUT) : dout_[slot].p;
-    const void *d_u = src_dev ? static_cast<const void *>(static_cast<const uint8_t *>(u) + c0 * UB) : din_[slot].p;
+    if (!dst_dev) pipe_.out_open(cs, slot);
+    void *d_out = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * OUT) : out_.dev[slot].p;
+    const void *d_u = src_dev ? static_cast<const void *>(static_cast<const uint8_t *>(u) + c0 * UB) : in_.dev[slot].p;
     if (hashing) {
       // offsets index the caller's array (bias 0) or the staged bytes of this chunk (bias b0)
-      const uint8_t *d_msgs = src_dev ? (m.offsets ? m.msgs : m.msgs + b0) : din_[slot].as<uint8_t>();
+      const uint8_t *d_msgs = src_dev ? (m.offsets ? m.msgs : m.msgs + b0) : in_.dev[slot].as<uint8_t>();
       const size_t bias = src_dev ? 0 : b0;
-      const uint8_t *d_aug = !has_aug ? nullptr : src_dev ? m.aug + c0 * m.aug_len : daug_[slot].as<uint8_t>();
-      const size_t *d_off = m.offsets ? doff_[slot].as<size_t>() : nullptr;
+      const uint8_t *d_aug = !has_aug ? nullptr : src_dev ? m.aug + c0 * m.aug_len : aug_.dev[slot].as<uint8_t>();
+      const size_t *d_off = m.offsets ? off_.dev[slot].as<size_t>() : nullptr;
       void *d_el = mapping ? u_.p : d_out;
       const size_t nel = cnt * count * G;
       hipLaunchKernelGGL(k_h2c_expand, dim3(nblk(cnt, 128)), dim3(128), 0, cs, d_msgs, d_off, bias, m.msg_len, d_aug,
@@ -684,17 +617,16 @@ void HashToCurve<G>::run(hipStream_t cs, int mode, const void *u, const H2cMsgs 
       d_u = d_el;
     }
     if (mapping) map_kernels(cs, d_u, d_out, cnt, count);
-    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    pipe_.computed(cs, slot);
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
-      MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * OUT, hipMemcpyDeviceToHost, d2h_));
-      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
-      if (k) drain(prev);  // chunk k - 1, while chunk k runs
-      prev = Pending{slot, c0, cnt};
+      pipe_.out_gate(slot);
+      pipe_.out_copy(slot, out_, cnt * OUT);
+      pipe_.out_close(slot);
+      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
     }
   }
-  if (!dst_dev) drain(prev);
-  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+  pend.flush();
+  pipe_.finish(cs);
 }
 
 template class HashToCurve<MSM_GROUP>;

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "env_size.hpp"
 #include "hash_to_curve_consts.hpp"
 
 #ifndef H2C_FN
@@ -153,21 +154,16 @@ inline void h2c_make_template(H2cTemplate &t, const uint8_t *dst, size_t dst_len
 
 // entries per chunk: MSM_H2C_CHUNK=<entries> overrides the default, read at each call
 inline size_t h2c_chunk() {
-  const char *e = getenv("MSM_H2C_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v > 0) return (size_t)v;
-  }
-  return H2C_CHUNK_DEFAULT;
+  const size_t e = env_size("MSM_H2C_CHUNK");
+  return e ? e : H2C_CHUNK_DEFAULT;
 }
-
 
 }  // namespace msm
 
 #ifndef MSM_H2C_HOST_ONLY
 #include <vector>
 
-#include "engine.hpp"
+#include "chunk_pipe.hpp"
 
 namespace msm {
 
@@ -189,16 +185,15 @@ struct H2cMsgs {
 };
 
 // One engine: the device buffers of a chunk (field elements, the images on the
-// isogenous curve, the points before the batch inversion, its levels) and for
-// host memory two pinned + two device staging buffers per direction.
+// isogenous curve, the points before the batch inversion, its levels, the
+// template) and for host memory staging lanes on the shared chunk pipe
+// (chunk_pipe.hpp): messages or elements, aug and offsets up, results down,
+// and a pinned lane for the template.
 template <int G>
 class HashToCurve {
  public:
   static constexpr size_t AFF = 96 * G, ELEM = 48 * G, XYZZ = 224 * G;
-  explicit HashToCurve(int device);
-  ~HashToCurve();
-  HashToCurve(const HashToCurve &) = delete;
-  HashToCurve &operator=(const HashToCurve &) = delete;
+  explicit HashToCurve(int device) : dev_(device), pipe_(device) {}
   // mode H2C_MAP: n * count field elements at u -> n affine points at dst;
   // H2C_FIELD: n messages -> n * count elements at dst; H2C_HASH: n messages
   // -> n affine points.  `cs` orders the kernels (the caller's stream when a
@@ -207,23 +202,18 @@ class HashToCurve {
   void run(hipStream_t cs, int mode, const void *u, const H2cMsgs &m, const H2cTemplate *tmpl, void *dst, size_t n,
            int count, bool src_dev, bool dst_dev);
   size_t device_bytes() const {
-    size_t b = r_.bytes + u_.bytes + e_.bytes + x_.bytes + lv_.bytes + tp_.bytes;
-    for (int i = 0; i < 2; ++i) b += din_[i].bytes + daug_[i].bytes + doff_[i].bytes + dout_[i].bytes;
-    return b;
+    return r_.bytes + u_.bytes + e_.bytes + x_.bytes + lv_.bytes + tp_.bytes + in_.device_bytes() +
+           aug_.device_bytes() + off_.device_bytes() + out_.device_bytes();
   }
   int device() const { return dev_; }
 
  private:
   int dev_;
   DevBuf r_, u_, e_, x_, lv_, tp_;  // uniform bytes, elements, images on E', points (xyzz), inversion levels, the template
-  DevBuf din_[2], daug_[2], doff_[2], dout_[2];
-  void *pin_in_[2] = {nullptr, nullptr}, *pin_aug_[2] = {nullptr, nullptr}, *pin_off_[2] = {nullptr, nullptr},
-       *pin_out_[2] = {nullptr, nullptr}, *pin_tp_[2] = {nullptr, nullptr};
-  size_t pin_in_bytes_ = 0, pin_aug_bytes_ = 0, pin_off_bytes_ = 0, pin_out_bytes_ = 0, pin_tp_bytes_ = 0;
-  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
-  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (the chunk buffers are reused)
-  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  Stage in_, aug_, off_, out_, tpl_;
+  // tpl_: pinned only, slot 0 goes into tp_ on the compute stream; the pipe comes
+  // last: it waits for the queued work before the buffers go
+  ChunkPipe pipe_;
   void map_kernels(hipStream_t s, const void *d_u, void *d_dst, size_t n, int count);
 };
 

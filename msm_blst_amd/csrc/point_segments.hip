@@ -196,58 +196,6 @@ static __global__ void __launch_bounds__(128)
 }
 
 template <int G>
-PointSegments<G>::PointSegments(int device) : dev_(device) {
-  DeviceGuard g(dev_);
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_meta_[i], hipEventDisableTiming));
-  }
-  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
-}
-
-template <int G>
-PointSegments<G>::~PointSegments() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(dev_);
-  // queued work may still read the staging, plan, table and level buffers
-  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
-  if (h2d_) (void)hipStreamSynchronize(h2d_);
-  if (d2h_) (void)hipStreamSynchronize(d2h_);
-  for (int i = 0; i < 2; ++i) {
-    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
-    if (ev_meta_[i]) (void)hipEventSynchronize(ev_meta_[i]);
-    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
-    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
-    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
-    if (ev_meta_[i]) (void)hipEventDestroy(ev_meta_[i]);
-    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
-    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
-    if (pin_meta_[i]) (void)hipHostFree(pin_meta_[i]);
-  }
-  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
-  if (h2d_) (void)hipStreamDestroy(h2d_);
-  if (d2h_) (void)hipStreamDestroy(d2h_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-template <int G>
-void PointSegments<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
-  if (bytes <= have) return;
-  for (int i = 0; i < 2; ++i) {
-    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
-    slots[i] = nullptr;
-  }
-  have = 0;
-  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
-  have = bytes;
-}
-
-template <int G>
 void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *scalars, const size_t *o, size_t k,
                            void *dst, int nbits, size_t stride, bool src_dev, bool dst_dev) {
   typedef typename FieldOf<G>::F SF;
@@ -274,26 +222,13 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
   lv_.ensure(std::max(msm ? ta_level_elems((size_t)(PM_ROWS - 1) * CP) : 0, ta_level_elems(C)) * ELEM);
   carry_.ensure(XYZZ);
   dmeta_.ensure(META);
-  ensure_pinned(pin_meta_, pin_meta_bytes_, META);
-  if (!src_dev && total) {
-    ensure_pinned(pin_in_, pin_in_bytes_, IN);
-    din_[0].ensure(IN);
-    din_[1].ensure(IN);
-  }
-  if (!dst_dev) {
-    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
-    dout_[0].ensure(C * AFF);
-    dout_[1].ensure(C * AFF);
-  }
-  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the table, partial and level buffers of the previous call
-  struct Pending {
-    int slot;
-    size_t off, cnt;
-  } prev{0, 0, 0};
-  auto drain = [&](const Pending &p) {
-    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
-    if (p.cnt) memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
-  };
+  plan_.ensure(META, false);
+  if (!src_dev && total) in_.ensure(IN);
+  if (!dst_dev) out_.ensure(C * AFF);
+  pipe_.begin(cs);  // the table, partial and level buffers of the previous call
+  auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {  // (a chunk may write no segment: cnt 0)
+    if (cnt) memcpy(static_cast<uint8_t *>(dst) + off * AFF, out_.pin[slot], cnt * AFF);
+  });
   const unsigned B = 128;
   Xyzz<SF> *part = xz_.as<Xyzz<SF>>();
   size_t j = 0, i = o[0], ck = 0;  // first segment not yet written, first point not yet summed
@@ -332,7 +267,7 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
     if (np > pmax || nseg > C || cnt > CP) throw std::runtime_error("point_segments: plan larger than its buffers");
     // ---- the plan and the sources go up ----
     MSM_HIP_CHECK(hipEventSynchronize(ev_meta_[slot]));  // chunk k - 2's plan has left the pinned slot
-    uint8_t *pm = static_cast<uint8_t *>(pin_meta_[slot]);
+    uint8_t *pm = static_cast<uint8_t *>(plan_.pin[slot]);
     if (np) memcpy(pm, meta_.data(), np * sizeof(SegMeta));
     if (nseg) memcpy(pm + pmax * sizeof(SegMeta), src_.data(), nseg * sizeof(uint32_t));
     if (np) MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.p, pm, np * sizeof(SegMeta), hipMemcpyHostToDevice, cs));
@@ -346,8 +281,8 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
     size_t d_stride = stride;
     if (cnt) {
       if (!src_dev) {
-        MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
-        uint8_t *w = static_cast<uint8_t *>(pin_in_[slot]);
+        pipe_.in_open(slot);
+        uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
         memcpy(w, static_cast<const uint8_t *>(points) + i * AFF, cnt * AFF);
         if (msm) {
           const uint8_t *sc = scalars + i * stride;
@@ -356,11 +291,10 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
             for (size_t q = 0; q < cnt; ++q) memcpy(w + PB + q * nb, sc + q * stride, nb);
           d_stride = nb;
         }
-        MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
-        MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], PB + cnt * nb, hipMemcpyHostToDevice, h2d_));
-        MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
-        MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
-        d_pts = din_[slot].as<uint8_t>();
+        pipe_.in_gate(slot);
+        pipe_.in_copy(slot, in_, PB + cnt * nb);
+        pipe_.in_close(cs, slot);
+        d_pts = in_.dev[slot].as<uint8_t>();
         d_sc = d_pts + PB;
       } else {
         d_pts = static_cast<const uint8_t *>(points) + i * AFF;
@@ -369,8 +303,8 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
     }
     void *d_dst = nullptr;
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
-      d_dst = dout_[slot].p;
+      pipe_.out_open(cs, slot);
+      d_dst = out_.dev[slot].p;
     } else {
       d_dst = static_cast<uint8_t *>(dst) + j * AFF;
     }
@@ -405,19 +339,18 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
     }
     carry = open_src != ~(size_t)0;
     if (carry) MSM_HIP_CHECK(hipMemcpyAsync(carry_.p, part + open_src, XYZZ, hipMemcpyDeviceToDevice, cs));
-    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    pipe_.computed(cs, slot);
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
-      if (nseg) MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, nseg * AFF, hipMemcpyDeviceToHost, d2h_));
-      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
-      if (ck) drain(prev);  // chunk k - 1, while chunk k runs
-      prev = Pending{slot, j, nseg};
+      pipe_.out_gate(slot);
+      if (nseg) pipe_.out_copy(slot, out_, nseg * AFF);
+      pipe_.out_close(slot);
+      pend.push(slot, j, nseg);  // chunk k - 1 is drained while chunk k runs
     }
     i = e;
     j = je;
   }
-  if (!dst_dev && ck) drain(prev);
-  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+  pend.flush();  // (nothing is held where no chunk ran)
+  pipe_.finish(cs);
 }
 
 template class PointSegments<MSM_GROUP>;

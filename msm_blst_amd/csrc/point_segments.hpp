@@ -10,7 +10,7 @@
 
 #include <vector>
 
-#include "engine.hpp"
+#include "chunk_pipe.hpp"
 #include "segments_plan.hpp"
 
 namespace msm {
@@ -24,18 +24,15 @@ struct SegMeta {
 // One engine: the table of a chunk (xyzz multiples, then their affine rows; the
 // partial sums reuse the xyzz buffer), the segment results, the level buffer of
 // the shared inversion tree (to_affine.hpp), the partial carried from one chunk
-// into the next, the plan of a chunk (two pinned slots, one device copy), and
-// for host memory two pinned + two device staging buffers per direction with
-// their own copy streams.  A staged input slot holds the points followed by
-// the scalars, packed (nbits + 7) / 8 bytes apart.
+// into the next, the plan of a chunk (two pinned slots with events of their
+// own, one device copy), and for host memory a staging lane per direction on
+// the shared chunk pipe (chunk_pipe.hpp).  A staged input slot holds the
+// points followed by the scalars, packed (nbits + 7) / 8 bytes apart.
 template <int G>
 class PointSegments {
  public:
   static constexpr size_t AFF = 96 * G, ROW = 112 * G, XYZZ = 224 * G, ELEM = 56 * G;
-  explicit PointSegments(int device);
-  ~PointSegments();
-  PointSegments(const PointSegments &) = delete;
-  PointSegments &operator=(const PointSegments &) = delete;
+  explicit PointSegments(int device) : dev_(device), ev_meta_(device), pipe_(device) {}
   // dst[j] = sum_{o[j] <= i < o[j + 1]} [k_i] P_i for j < k, o = offsets (host,
   // k + 1 values, non-decreasing).  k_i = the low nbits bits of the
   // little-endian scalar at scalars + i stride (0 < nbits <= 256, stride >=
@@ -47,23 +44,19 @@ class PointSegments {
   void run(hipStream_t cs, const void *points, const uint8_t *scalars, const size_t *offsets, size_t k, void *dst,
            int nbits, size_t stride, bool src_dev, bool dst_dev);
   size_t device_bytes() const {
-    return xz_.bytes + rows_.bytes + res_.bytes + lv_.bytes + carry_.bytes + dmeta_.bytes + din_[0].bytes +
-           din_[1].bytes + dout_[0].bytes + dout_[1].bytes;
+    return xz_.bytes + rows_.bytes + res_.bytes + lv_.bytes + carry_.bytes + dmeta_.bytes + in_.device_bytes() +
+           out_.device_bytes();
   }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf xz_, rows_, res_, lv_, carry_, dmeta_, din_[2], dout_[2];
-  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr}, *pin_meta_[2] = {nullptr, nullptr};
-  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0, pin_meta_bytes_ = 0;
-  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
-  hipEvent_t ev_meta_[2] = {nullptr, nullptr};  // the plan of chunk k - 2 has left its pinned slot
-  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (table, partial and level buffers are reused)
-  std::vector<SegMeta> meta_;     // the plan of the chunk being queued
-  std::vector<uint32_t> src_;     // per segment written by the chunk: the partial that holds its sum, or ~0 (empty)
-  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  DevBuf xz_, rows_, res_, lv_, carry_, dmeta_;
+  Stage in_, out_, plan_;      // plan_: pinned only, copied into dmeta_ on the compute stream
+  std::vector<SegMeta> meta_;  // the plan of the chunk being queued
+  std::vector<uint32_t> src_;  // per segment written by the chunk: the partial that holds its sum, or ~0 (empty)
+  EventPair ev_meta_;          // the plan of chunk k - 2 has left its pinned slot
+  ChunkPipe pipe_;             // (last: it waits for the queued work before the buffers go)
 };
 
 }  // namespace msm

@@ -95,54 +95,6 @@ static __global__ void __launch_bounds__(128, 2)
 }
 
 template <int G>
-PointsMult<G>::PointsMult(int device) : dev_(device) {
-  DeviceGuard g(dev_);
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
-  }
-  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
-}
-
-template <int G>
-PointsMult<G>::~PointsMult() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(dev_);
-  // queued work may still read the staging, table and level buffers
-  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
-  if (h2d_) (void)hipStreamSynchronize(h2d_);
-  if (d2h_) (void)hipStreamSynchronize(d2h_);
-  for (int i = 0; i < 2; ++i) {
-    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
-    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
-    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
-    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
-    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
-    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
-  }
-  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
-  if (h2d_) (void)hipStreamDestroy(h2d_);
-  if (d2h_) (void)hipStreamDestroy(d2h_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-template <int G>
-void PointsMult<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
-  if (bytes <= have) return;
-  for (int i = 0; i < 2; ++i) {
-    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
-    slots[i] = nullptr;
-  }
-  have = 0;
-  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
-  have = bytes;
-}
-
-template <int G>
 void PointsMult<G>::table(hipStream_t s, const void *d_points, size_t np) {
   typedef typename FieldOf<G>::F SF;
   static_assert(sizeof(Aff<SF>) == ROW && sizeof(Xyzz<SF>) == XYZZ && sizeof(SF) == ELEM, "stored sizes");
@@ -181,25 +133,12 @@ void PointsMult<G>::run(hipStream_t cs, const void *points, const uint8_t *scala
   rows_.ensure(PM_ROWS * T * ROW);
   xz_.ensure(std::max((size_t)(PM_ROWS - 1) * T, C) * XYZZ);
   lv_.ensure(std::max(ta_level_elems((size_t)(PM_ROWS - 1) * T), ta_level_elems(C)) * ELEM);
-  if (!src_dev) {
-    ensure_pinned(pin_in_, pin_in_bytes_, IN);
-    din_[0].ensure(IN);
-    din_[1].ensure(IN);
-  }
-  if (!dst_dev) {
-    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
-    dout_[0].ensure(C * AFF);
-    dout_[1].ensure(C * AFF);
-  }
-  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the table and level buffers of the previous call
-  struct Pending {
-    int slot;
-    size_t off, cnt;
-  } prev{0, 0, 0};
-  auto drain = [&](const Pending &p) {
-    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
-    memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
-  };
+  if (!src_dev) in_.ensure(IN);
+  if (!dst_dev) out_.ensure(C * AFF);
+  pipe_.begin(cs);  // the table and level buffers of the previous call
+  auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {
+    memcpy(static_cast<uint8_t *>(dst) + off * AFF, out_.pin[slot], cnt * AFF);
+  });
   size_t k = 0;
   for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
     const size_t cnt = std::min(C, n - c0);
@@ -209,43 +148,41 @@ void PointsMult<G>::run(hipStream_t cs, const void *points, const uint8_t *scala
     size_t d_stride = stride;
     void *d_dst;
     if (!src_dev) {
-      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
-      uint8_t *w = static_cast<uint8_t *>(pin_in_[slot]);
+      pipe_.in_open(slot);
+      uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
       memcpy(w, static_cast<const uint8_t *>(points) + (one_point ? 0 : c0 * AFF), np * AFF);
       const uint8_t *sc = scalars + c0 * stride;
       if (stride == nb) memcpy(w + PB, sc, cnt * nb);
       else  // only the nb bytes of each scalar: nothing past the last one is read, and the slot stays small
         for (size_t i = 0; i < cnt; ++i) memcpy(w + PB + i * nb, sc + i * stride, nb);
       d_stride = nb;
-      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
-      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], PB + cnt * nb, hipMemcpyHostToDevice, h2d_));
-      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
-      d_pts = din_[slot].as<uint8_t>();
+      pipe_.in_gate(slot);
+      pipe_.in_copy(slot, in_, PB + cnt * nb);
+      pipe_.in_close(cs, slot);
+      d_pts = in_.dev[slot].as<uint8_t>();
       d_sc = d_pts + PB;
     } else {
       d_pts = static_cast<const uint8_t *>(points) + (one_point ? 0 : c0 * AFF);
       d_sc = scalars + c0 * stride;
     }
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
-      d_dst = dout_[slot].p;
+      pipe_.out_open(cs, slot);
+      d_dst = out_.dev[slot].p;
     } else {
       d_dst = static_cast<uint8_t *>(dst) + c0 * AFF;
     }
     if (!one_point || k == 0) table(cs, d_pts, np);  // one point: its rows serve every chunk
     ladder(cs, np, d_sc, d_dst, cnt, nbits, d_stride);
-    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    pipe_.computed(cs, slot);
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
-      MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * AFF, hipMemcpyDeviceToHost, d2h_));
-      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
-      if (k) drain(prev);  // chunk k - 1, while chunk k runs
-      prev = Pending{slot, c0, cnt};
+      pipe_.out_gate(slot);
+      pipe_.out_copy(slot, out_, cnt * AFF);
+      pipe_.out_close(slot);
+      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
     }
   }
-  if (!dst_dev) drain(prev);
-  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+  pend.flush();
+  pipe_.finish(cs);
 }
 
 template class PointsMult<MSM_GROUP>;

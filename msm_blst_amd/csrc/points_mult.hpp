@@ -5,9 +5,8 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
-#include "engine.hpp"
+#include "chunk_pipe.hpp"
 
 namespace msm {
 
@@ -16,27 +15,20 @@ constexpr int PM_ROWS = 8;  // 1P .. 8P: signed 4-bit windows
 
 // points per chunk: MSM_POINTS_MULT_CHUNK=<points> overrides the default, read at each call
 inline size_t pm_chunk() {
-  const char *e = getenv("MSM_POINTS_MULT_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v > 0) return (size_t)v;
-  }
-  return PM_CHUNK_DEFAULT;
+  const size_t e = env_size("MSM_POINTS_MULT_CHUNK");
+  return e ? e : PM_CHUNK_DEFAULT;
 }
 
 // One engine: the table of a chunk (xyzz multiples, then their affine rows),
 // the level buffer of the shared inversion tree (to_affine.hpp), and for host
-// memory two pinned + two device staging buffers per direction with their own
-// copy streams.  A staged input slot holds the points followed by the scalars,
-// packed (nbits + 7) / 8 bytes apart.
+// memory a staging lane per direction on the shared chunk pipe
+// (chunk_pipe.hpp).  A staged input slot holds the points followed by the
+// scalars, packed (nbits + 7) / 8 bytes apart.
 template <int G>
 class PointsMult {
  public:
   static constexpr size_t AFF = 96 * G, ROW = 112 * G, XYZZ = 224 * G, ELEM = 56 * G;
-  explicit PointsMult(int device);
-  ~PointsMult();
-  PointsMult(const PointsMult &) = delete;
-  PointsMult &operator=(const PointsMult &) = delete;
+  explicit PointsMult(int device) : dev_(device), pipe_(device) {}
   // dst[i] = [k_i] P_i for i < n, k_i = the low nbits bits of the little-endian
   // scalar at scalars + i stride (0 < nbits <= 256, stride >= (nbits + 7) / 8).
   // one_point: `points` holds one point, used for every scalar.  points and
@@ -46,20 +38,14 @@ class PointsMult {
   // queued on cs; host destination: returns with the data in dst.
   void run(hipStream_t cs, const void *points, const uint8_t *scalars, void *dst, size_t n, int nbits, size_t stride,
            bool one_point, bool src_dev, bool dst_dev);
-  size_t device_bytes() const {
-    return xz_.bytes + rows_.bytes + lv_.bytes + din_[0].bytes + din_[1].bytes + dout_[0].bytes + dout_[1].bytes;
-  }
+  size_t device_bytes() const { return xz_.bytes + rows_.bytes + lv_.bytes + in_.device_bytes() + out_.device_bytes(); }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf xz_, rows_, lv_, din_[2], dout_[2];  // xyzz multiples / ladder results, affine rows, tree levels, staging
-  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr};
-  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0;
-  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
-  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (table and level buffers are reused)
-  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  DevBuf xz_, rows_, lv_;  // xyzz multiples / ladder results, affine rows, tree levels
+  Stage in_, out_;
+  ChunkPipe pipe_;  // (last: it waits for the queued work before the buffers go)
   // the rows of `np` points (row m of point t at rows_[(m - 1) np + t])
   void table(hipStream_t s, const void *d_points, size_t np);
   // one chunk, device to device, on a table of np rows per multiple (np == 1: every lane reads point 0's)

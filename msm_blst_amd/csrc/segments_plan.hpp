@@ -9,9 +9,10 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <algorithm>
+
+#include "env_size.hpp"
 
 namespace msm {
 
@@ -25,19 +26,10 @@ constexpr size_t SEG_LANES = (size_t)256 * 4 * 2 * 64;
 constexpr size_t SEG_POINT_BYTES = 8 * 112 + 7 * 224 + 224 + 72;
 constexpr size_t SEG_CHUNK_BUDGET = (size_t)3 << 30;  // bytes of the above per chunk
 
-inline size_t seg_env(const char *name) {
-  const char *e = getenv(name);
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v > 0) return (size_t)v;
-  }
-  return 0;
-}
-
 // points (and segments written) per chunk: MSM_POINTS_SEGMENTS_CHUNK=<points>
 // overrides the default, read at each call
 inline size_t seg_chunk(int group) {
-  const size_t e = seg_env("MSM_POINTS_SEGMENTS_CHUNK");
+  const size_t e = env_size("MSM_POINTS_SEGMENTS_CHUNK");
   return e ? e : SEG_CHUNK_BUDGET / (SEG_POINT_BYTES * (size_t)group);
 }
 
@@ -49,7 +41,7 @@ inline size_t seg_chunk(int group) {
 // on G1 and 11 % on G2, and half a piece per lane loses to both.
 // MSM_POINTS_SEGMENTS_PIECE=<points> overrides it, read at each call.
 inline size_t seg_piece_len(size_t m, int group) {
-  const size_t e = seg_env("MSM_POINTS_SEGMENTS_PIECE");
+  const size_t e = env_size("MSM_POINTS_SEGMENTS_PIECE");
   if (e) return std::min(e, SEG_PIECE_MAX);
   const size_t lanes = SEG_LANES / (size_t)group;
   return std::min(std::max(m / lanes, (size_t)1), SEG_PIECE_MAX);

@@ -276,54 +276,6 @@ static __global__ void __launch_bounds__(128)
   });
 }
 
-template <int G>
-ToAffine<G>::ToAffine(int device) : dev_(device) {
-  DeviceGuard g(dev_);
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&h2d_, hipStreamNonBlocking));
-  MSM_HIP_CHECK(hipStreamCreateWithFlags(&d2h_, hipStreamNonBlocking));
-  for (int i = 0; i < 2; ++i) {
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_comp_[i], hipEventDisableTiming));
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_d2h_[i], hipEventDisableTiming));
-  }
-  MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_busy_, hipEventDisableTiming));
-}
-
-template <int G>
-ToAffine<G>::~ToAffine() {
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(dev_);
-  // queued work may still read the staging and level buffers
-  if (ev_busy_) (void)hipEventSynchronize(ev_busy_);
-  if (h2d_) (void)hipStreamSynchronize(h2d_);
-  if (d2h_) (void)hipStreamSynchronize(d2h_);
-  for (int i = 0; i < 2; ++i) {
-    if (ev_comp_[i]) (void)hipEventSynchronize(ev_comp_[i]);
-    if (ev_h2d_[i]) (void)hipEventDestroy(ev_h2d_[i]);
-    if (ev_comp_[i]) (void)hipEventDestroy(ev_comp_[i]);
-    if (ev_d2h_[i]) (void)hipEventDestroy(ev_d2h_[i]);
-    if (pin_in_[i]) (void)hipHostFree(pin_in_[i]);
-    if (pin_out_[i]) (void)hipHostFree(pin_out_[i]);
-  }
-  if (ev_busy_) (void)hipEventDestroy(ev_busy_);
-  if (h2d_) (void)hipStreamDestroy(h2d_);
-  if (d2h_) (void)hipStreamDestroy(d2h_);
-  if (prev >= 0) (void)hipSetDevice(prev);
-}
-
-template <int G>
-void ToAffine<G>::ensure_pinned(void **slots, size_t &have, size_t bytes) {
-  if (bytes <= have) return;
-  for (int i = 0; i < 2; ++i) {
-    if (slots[i]) (void)hipHostFree(slots[i]);  // (waits for the copies that use it)
-    slots[i] = nullptr;
-  }
-  have = 0;
-  for (int i = 0; i < 2; ++i) MSM_HIP_CHECK(hipHostMalloc(&slots[i], bytes, hipHostMallocDefault));
-  have = bytes;
-}
-
 // the tree over n points at d_src (kind: every point source of to_affine.hpp), all
 // in device memory; lv holds ta_level_elems(n) elements
 template <int G, int SRC>
@@ -388,26 +340,13 @@ void ToAffine<G>::run(hipStream_t cs, const void *src_dev_ptr, const std::vector
   size_t elems = 0;
   for (size_t v : ta_levels(C)) elems += v;
   lv_.ensure(elems * ELEM);
-  if (!src_dev) {
-    ensure_pinned(pin_in_, pin_in_bytes_, C * JAC);
-    din_[0].ensure(C * JAC);
-    din_[1].ensure(C * JAC);
-  }
-  if (!dst_dev) {
-    ensure_pinned(pin_out_, pin_out_bytes_, C * AFF);
-    dout_[0].ensure(C * AFF);
-    dout_[1].ensure(C * AFF);
-  }
-  MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_busy_, 0));  // the level buffers of the previous call
-  size_t ri = 0, roff = 0;                             // gather cursor: run, point within it
-  struct Pending {
-    int slot;
-    size_t off, cnt;
-  } prev{0, 0, 0};
-  auto drain = [&](const Pending &p) {
-    MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[p.slot]));
-    memcpy(static_cast<uint8_t *>(dst) + p.off * AFF, pin_out_[p.slot], p.cnt * AFF);
-  };
+  if (!src_dev) in_.ensure(C * JAC);
+  if (!dst_dev) out_.ensure(C * AFF);
+  pipe_.begin(cs);          // the level buffers of the previous call
+  size_t ri = 0, roff = 0;  // gather cursor: run, point within it
+  auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {
+    memcpy(static_cast<uint8_t *>(dst) + off * AFF, out_.pin[slot], cnt * AFF);
+  });
   size_t k = 0;
   for (size_t c0 = 0; c0 < n; c0 += C, ++k) {
     const size_t cnt = std::min(C, n - c0);
@@ -415,8 +354,8 @@ void ToAffine<G>::run(hipStream_t cs, const void *src_dev_ptr, const std::vector
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));  // chunk k - 2 has left the pinned slot
-      uint8_t *w = static_cast<uint8_t *>(pin_in_[slot]);
+      pipe_.in_open(slot);
+      uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
       for (size_t left = cnt; left;) {  // the gather writes straight into pinned memory
         if (ri >= runs.size()) throw std::runtime_error("to_affine: pointer runs do not cover the points");
         const size_t take = std::min(left, runs[ri].count - roff);
@@ -424,32 +363,30 @@ void ToAffine<G>::run(hipStream_t cs, const void *src_dev_ptr, const std::vector
         w += take * JAC, left -= take, roff += take;
         if (roff == runs[ri].count) ++ri, roff = 0;
       }
-      MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));  // chunk k - 2's kernels have read din_[slot]
-      MSM_HIP_CHECK(hipMemcpyAsync(din_[slot].p, pin_in_[slot], cnt * JAC, hipMemcpyHostToDevice, h2d_));
-      MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
-      d_src = din_[slot].p;
+      pipe_.in_gate(slot);
+      pipe_.in_copy(slot, in_, cnt * JAC);
+      pipe_.in_close(cs, slot);
+      d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src_dev_ptr) + c0 * JAC;
     }
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0));  // chunk k - 2 has left dout_[slot]
-      d_dst = dout_[slot].p;
+      pipe_.out_open(cs, slot);
+      d_dst = out_.dev[slot].p;
     } else {
       d_dst = static_cast<uint8_t *>(dst) + c0 * AFF;
     }
     kernels(cs, d_src, d_dst, cnt);
-    MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs));
+    pipe_.computed(cs, slot);
     if (!dst_dev) {
-      MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
-      MSM_HIP_CHECK(hipMemcpyAsync(pin_out_[slot], dout_[slot].p, cnt * AFF, hipMemcpyDeviceToHost, d2h_));
-      MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
-      if (k) drain(prev);  // chunk k - 1, while chunk k runs
-      prev = Pending{slot, c0, cnt};
+      pipe_.out_gate(slot);
+      pipe_.out_copy(slot, out_, cnt * AFF);
+      pipe_.out_close(slot);
+      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
     }
   }
-  if (!dst_dev) drain(prev);
-  MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs));
+  pend.flush();
+  pipe_.finish(cs);
 }
 
 template class ToAffine<MSM_GROUP>;

@@ -5,11 +5,10 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <vector>
 
-#include "engine.hpp"
+#include "chunk_pipe.hpp"
 
 namespace msm {
 
@@ -26,12 +25,8 @@ constexpr size_t TA_CHUNK_DEFAULT = (size_t)1 << 18;
 
 // points per chunk: MSM_TO_AFFINE_CHUNK=<points> overrides the default, read at each call
 inline size_t ta_chunk() {
-  const char *e = getenv("MSM_TO_AFFINE_CHUNK");
-  if (e && *e) {
-    const long long v = atoll(e);
-    if (v > 0) return (size_t)v;
-  }
-  return TA_CHUNK_DEFAULT;
+  const size_t e = env_size("MSM_TO_AFFINE_CHUNK");
+  return e ? e : TA_CHUNK_DEFAULT;
 }
 
 // sizes of the levels above n points (at least one level for n >= 1)
@@ -69,8 +64,8 @@ enum {
 template <int G>
 void ta_tree(hipStream_t s, void *lv, size_t lv_bytes, int kind, const void *d_src, void *d_dst, size_t n);
 
-// One engine: level buffers, and for host memory two pinned + two device
-// staging buffers per direction with their own copy streams.
+// One engine: level buffers, and for host memory a staging lane per direction
+// on the shared chunk pipe (chunk_pipe.hpp).
 template <int G>
 class ToAffine {
  public:
@@ -81,10 +76,7 @@ class ToAffine {
     const uint8_t *p;
     size_t count;
   };
-  explicit ToAffine(int device);
-  ~ToAffine();
-  ToAffine(const ToAffine &) = delete;
-  ToAffine &operator=(const ToAffine &) = delete;
+  explicit ToAffine(int device) : dev_(device), pipe_(device) {}
   // n Jacobians -> n affine points.  src: device memory (src_dev), or host
   // memory named by `runs` (ascending, covering [0, n)).  dst: flat, host or
   // device.  `cs` orders the kernels (the caller's stream when a side is device
@@ -92,18 +84,14 @@ class ToAffine {
   // queued on cs; host destination: returns with the data in dst.
   void run(hipStream_t cs, const void *src_dev_ptr, const std::vector<Run> &runs, void *dst, size_t n, bool src_dev,
            bool dst_dev);
-  size_t device_bytes() const { return lv_.bytes + din_[0].bytes + din_[1].bytes + dout_[0].bytes + dout_[1].bytes; }
+  size_t device_bytes() const { return lv_.bytes + in_.device_bytes() + out_.device_bytes(); }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf lv_, din_[2], dout_[2];
-  void *pin_in_[2] = {nullptr, nullptr}, *pin_out_[2] = {nullptr, nullptr};
-  size_t pin_in_bytes_ = 0, pin_out_bytes_ = 0;
-  hipStream_t h2d_ = nullptr, d2h_ = nullptr;
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr}, ev_comp_[2] = {nullptr, nullptr}, ev_d2h_[2] = {nullptr, nullptr};
-  hipEvent_t ev_busy_ = nullptr;  // the last kernel of the previous call (level buffers are reused)
-  void ensure_pinned(void **slots, size_t &have, size_t bytes);
+  DevBuf lv_;
+  Stage in_, out_;
+  ChunkPipe pipe_;  // (last: it waits for the queued work before the buffers go)
   void kernels(hipStream_t s, const void *d_src, void *d_dst, size_t n);
 };
 
