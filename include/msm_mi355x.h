@@ -608,6 +608,47 @@ int msm_points_hash(int group, int device, void *dst_affine, const void *msgs, c
  * out_len, NULL DST with DST_len > 0. */
 int msm_h2c_dst_prime(byte *out, size_t *out_len, const byte *DST, size_t DST_len);
 
+/* ---- bulk pairings (replaces a loop over the reference's one-pair blst_miller_loop /
+ * blst_fp12_mul / blst_final_exp: ref src/pairing.c:181-262 and 371-404) ----
+ * A pair is (P, Q): P a G1 and Q a G2 affine point in blst's Montgomery layout (96 and
+ * 192 bytes, infinity the all-zero point).  A GT value is a blst_fp12 (576 bytes,
+ * canonical).  msm_pairing_segments: dst[j] = blst_final_exp of the product of
+ * blst_miller_loop(Q_i, P_i) over offsets[j] <= i < offsets[j + 1], byte for byte;
+ * offsets is a HOST array of nsegments + 1 non-decreasing values, or NULL for nsegments
+ * segments of one pair each (a plain bulk pairing).  A pair whose P or Q is the all-zero
+ * point contributes the factor one at every position; an empty segment gives one.
+ * Nothing is validated: the points must be on the curve, and for points outside the
+ * prime-order subgroups the value is unspecified (the call completes).  Under
+ * MSM_PAIRING_MILLER_ONLY the final exponentiation is skipped: dst[j] is the product of
+ * the Miller values, which equals the reference's only up to factors the final
+ * exponentiation removes.  dst_fp12 may be NULL when only the verdicts are wanted.
+ * is_one (nsegments bytes) and nfail are HOST memory and may be NULL: is_one[j] = 1 when
+ * value j is one, *nfail = the number of values that are not; a call that passes either
+ * returns only after they are written.  msm_fp12_final_exp: dst[i] = blst_final_exp of
+ * the canonical non-zero value src[i] (a zero input is unspecified but completes).
+ * p / q (one memory space), src and dst each in host or device memory (device pointers
+ * 8-byte aligned), on HIP device `device`.
+ * nsegments == 0 / n == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work:
+ * NULL p / q with pairs to read, NULL src, NULL dst with neither is_one nor nfail, a
+ * decreasing offset, unknown flag bits, is_one / nfail under MSM_PAIRING_MILLER_ONLY, a
+ * host dst overlapping a host source.  MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP
+ * failure; a host dst is then zero-filled, is_one filled with 0 and *nfail set to the
+ * number of values.  Streams as msm_points_to_affine.  On the GPU: csrc/pairing.hip
+ * (DESIGN section 21); chunks of at most 2^16 pairs (MSM_PAIRING_CHUNK=<pairs>
+ * overrides, read at each call; a segment may span chunks), pieces of at most
+ * MSM_PAIRING_PIECE=<pairs> pairs, host memory through two pinned staging buffers per
+ * lane.  Thread-safe per call (an engine pool keyed by device, counted by
+ * msm_engine_cache_stats(), freed by msm_release_engine_cache()). */
+enum { MSM_PAIRING_MILLER_ONLY = 1 }; /* flags: skip the final exponentiation */
+int msm_pairing_segments(int device, void *dst_fp12, uint8_t *is_one, size_t *nfail, const void *p_affine,
+                         const void *q_affine, const size_t *offsets, size_t nsegments, int flags, int src_on_device,
+                         int dst_on_device, void *hip_stream);
+int msm_fp12_final_exp(int device, void *dst_fp12, uint8_t *is_one, size_t *nfail, const void *src_fp12, size_t n,
+                       int src_on_device, int dst_on_device, void *hip_stream);
+/* host only: the piece length msm_pairing_segments uses for npairs pairs (MSM_PAIRING_PIECE and
+ * MSM_PAIRING_CHUNK as set at the call) */
+size_t msm_pairing_piece(size_t npairs);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

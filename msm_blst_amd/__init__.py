@@ -24,6 +24,8 @@ Mirrors:
   ps_hash_to_curve, ps_hash_to_field, ps_map_to_curve blst_hash_to_g{1,2} / blst_encode_to_g{1,2} / blst_map_to_g{1,2} and
                                                       hash_to_field (ref map_to_g1.c:285-453, map_to_g2.c:173-401,
                                                       hash_to_field.c:51-154), bulk, on the GPU
+  ps_pairing, ps_pairing_segments, ps_pairing_check,  blst_miller_loop / blst_fp12_mul / blst_final_exp / blst_fp12_is_one
+  ps_final_exp                                        (ref pairing.c:181-262, 371-404), bulk, on the GPU
 """
 import ctypes
 
@@ -36,6 +38,7 @@ __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext
            "compress", "to_affine", "ps_to_affine", "to_affine_levels", "ps_decode", "ps_mult", "ps_encode",
            "ps_msm_segments", "ps_sum_segments", "segments_plan",
            "ps_map_to_curve", "ps_hash_to_field", "ps_hash_to_curve", "h2c_dst_prime",
+           "ps_pairing", "ps_pairing_segments", "ps_pairing_check", "ps_final_exp", "fp12_one", "FP12_BYTES",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -45,6 +48,8 @@ DECODE_CHECK_GROUP = 1                 # MSM_DECODE_CHECK_GROUP
 MULT_ONE_POINT = 1                     # MSM_MULT_ONE_POINT
 SRC_AFFINE, SRC_JACOBIAN = 0, 1        # MSM_SRC_*: 96 G / 144 G bytes per point
 H2C_ENCODE = 1                         # MSM_H2C_ENCODE
+PAIRING_MILLER_ONLY = 1                # MSM_PAIRING_MILLER_ONLY
+FP12_BYTES = 576                       # a GT value: blst_fp12
 
 
 def device_count():
@@ -449,6 +454,104 @@ def h2c_dst_prime(dst_tag):
     n = ctypes.c_size_t(0)
     check(lib().msm_h2c_dst_prime(out, ctypes.byref(n), tag, len(tag)))
     return bytes(out[:n.value])
+
+
+_P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+
+
+def fp12_one():
+    """blst_fp12_one(): the 576 bytes of the GT value one (2^384 mod p in blst's limbs, then zeros)."""
+    return ((1 << 384) % _P).to_bytes(48, "little") + bytes(FP12_BYTES - 48)
+
+
+def _pair_sources(p, q, n, src_on_device):
+    if src_on_device:
+        return p, q
+    bufs = []
+    for data, size, what in ((p, POINT_BYTES[1], "p"), (q, POINT_BYTES[2], "q")):
+        b = _buf(data)
+        have = len(b) if hasattr(b, "__len__") else ctypes.sizeof(b)
+        if have < size * n:
+            raise ValueError(f"{have} bytes of {what} given, {size * n} needed")
+        bufs.append(b)
+    return bufs
+
+
+def _pairing(p, q, offs, k, n, final_exp, check_only, src_on_device, dst, device, stream):
+    pb, qb = _pair_sources(p, q, n, src_on_device)
+    o = (ctypes.c_size_t * (k + 1))(*offs) if offs is not None else None
+    flags = 0 if final_exp else PAIRING_MILLER_ONLY
+    sd = int(bool(src_on_device))
+    if check_only:
+        verdict = (ctypes.c_uint8 * max(k, 1))()
+        check(lib().msm_pairing_segments(device, None, verdict, None, pb, qb, o, k, flags, sd, 0, stream))
+        return bytes(verdict[:k])
+    if dst is not None:
+        check(lib().msm_pairing_segments(device, dst, None, None, pb, qb, o, k, flags, sd, 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (FP12_BYTES * k))()
+    check(lib().msm_pairing_segments(device, out, None, None, pb, qb, o, k, flags, sd, 0, stream))
+    return bytes(out)
+
+
+def _pair_offsets(offsets):
+    offs = [int(v) for v in offsets]
+    if not offs:
+        raise ValueError("offsets must hold nsegments + 1 values")
+    if offs[0] < 0 or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError("offsets must be non-negative and non-decreasing")
+    k = len(offs) - 1
+    return offs, k, (offs[-1] if k else 0)
+
+
+def ps_pairing(p, q, n, *, final_exp=True, src_on_device=False, dst=None, device=0, stream=None):
+    """n pairings e(P_i, Q_i) in one call (msm_pairing_segments without offsets): n GT
+    values of FP12_BYTES bytes, byte for byte blst_final_exp(blst_miller_loop(Q_i, P_i)).
+    p: n G1 affine points (96 B), q: n G2 affine points (192 B); a pair with infinity on
+    either side gives one.  final_exp=False returns the Miller values (equal to the
+    reference's only after the final exponentiation).  Host sources are bytes-like
+    objects, device sources (src_on_device, both) device pointers.  With dst=<device
+    pointer> the values are written there, ordered on `stream`, and None is returned."""
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    return _pairing(p, q, None, n, n, final_exp, False, src_on_device, dst, device, stream)
+
+
+def ps_pairing_segments(p, q, offsets, *, final_exp=True, src_on_device=False, dst=None, device=0, stream=None):
+    """k pairing products in one call (msm_pairing_segments): out[j] = the final
+    exponentiation of the product of the Miller values of the pairs offsets[j] <= i <
+    offsets[j + 1] (one for an empty segment).  offsets as in ps_msm_segments; the other
+    arguments as in ps_pairing."""
+    offs, k, n = _pair_offsets(offsets)
+    return _pairing(p, q, offs, k, n, final_exp, False, src_on_device, dst, device, stream)
+
+
+def ps_pairing_check(p, q, offsets, *, src_on_device=False, device=0, stream=None):
+    """The verdicts of k pairing products (msm_pairing_segments with dst NULL): bytes of
+    k values, 1 where the product of segment j is one."""
+    offs, k, n = _pair_offsets(offsets)
+    return _pairing(p, q, offs, k, n, True, True, src_on_device, None, device, stream)
+
+
+def ps_final_exp(f, n, *, src_on_device=False, dst=None, device=0, stream=None):
+    """n final exponentiations (msm_fp12_final_exp): blst_final_exp of n canonical
+    non-zero blst_fp12 values.  Arguments as in ps_pairing."""
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if src_on_device:
+        src = f
+    else:
+        src = _buf(f)
+        have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+        if have < FP12_BYTES * n:
+            raise ValueError(f"{have} bytes of Fp12 values given, {FP12_BYTES * n} needed")
+    sd = int(bool(src_on_device))
+    if dst is not None:
+        check(lib().msm_fp12_final_exp(device, dst, None, None, src, n, sd, 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (FP12_BYTES * n))()
+    check(lib().msm_fp12_final_exp(device, out, None, None, src, n, sd, 0, stream))
+    return bytes(out)
 
 
 def to_affine_levels(n):

@@ -139,6 +139,10 @@ def lib():
     L.msm_hash_to_field.argtypes = [i32, i32, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, i32, i32, vp]
     L.msm_points_hash.argtypes = [i32, i32, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, i32, i32, vp]
     L.msm_h2c_dst_prime.argtypes = [vp, vp, vp, sz]
+    L.msm_pairing_segments.argtypes = [i32, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, vp]
+    L.msm_fp12_final_exp.argtypes = [i32, vp, vp, vp, vp, sz, i32, i32, vp]
+    L.msm_pairing_piece.argtypes = [sz]
+    L.msm_pairing_piece.restype = sz
     _lib = L
     return L
 

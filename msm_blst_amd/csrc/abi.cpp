@@ -22,6 +22,7 @@
 #include "engine.hpp"
 #include "hash_to_curve.hpp"
 #include "multi.hpp"
+#include "pairing.hpp"
 #include "point_segments.hpp"
 #include "points_mult.hpp"
 #include "pool.hpp"
@@ -600,6 +601,68 @@ int hash_to_curve_checked(int group, int dev, int mode, void *dst, const void *u
   }
 }
 
+// ---- bulk pairings (a loop over ref pairing.c:181-262 miller_loop_n and 371-404 final_exp per pair) ----
+// src: the Fp12 values of msm_fp12_final_exp (then p, q and offsets are unused), else NULL.
+int pairing_checked(int dev, void *dst, uint8_t *is_one, size_t *nfail, const void *p, const void *q, const void *src,
+                    const size_t *offsets, size_t k, int flags, bool fe_only, bool src_dev, bool dst_dev,
+                    hipStream_t user) {
+  if (flags & ~MSM_PAIRING_MILLER_ONLY) return fail(MSM_E_ARG, "unknown flag bits");
+  const bool fe = !(flags & MSM_PAIRING_MILLER_ONLY);
+  if (!fe && (is_one || nfail)) return fail(MSM_E_ARG, "is_one / nfail under MSM_PAIRING_MILLER_ONLY");
+  if (k == 0) return MSM_OK;  // nothing touched
+  if (!dst && !is_one && !nfail) return fail(MSM_E_ARG, "null dst without is_one / nfail");
+  if (k > ((size_t)1 << 40)) return fail(MSM_E_ARG, "nsegments out of range");
+  if (!dst) dst_dev = false;
+  const size_t GT = Pairing::GT;
+  size_t first = 0, last = k;  // the pairs read
+  if (fe_only) {
+    if (!src) return fail(MSM_E_ARG, "null src");
+    if (!src_dev && dst && !dst_dev && ranges_overlap(src, k * GT, dst, k * GT))
+      return fail(MSM_E_ARG, "source and destination overlap");
+    if (src_dev && ((uintptr_t)src & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  } else {
+    if (offsets) {
+      if (!seg_offsets_ok(offsets, k)) return fail(MSM_E_ARG, "offsets decrease");
+      first = offsets[0], last = offsets[k];
+      if (last > ((size_t)1 << 40)) return fail(MSM_E_ARG, "offsets out of range");
+    }
+    if (last > first && (!p || !q)) return fail(MSM_E_ARG, "null p / q");
+    if (!src_dev && dst && !dst_dev && last > first &&
+        (ranges_overlap(p, last * Pairing::P_AFF, dst, k * GT) || ranges_overlap(q, last * Pairing::Q_AFF, dst, k * GT)))
+      return fail(MSM_E_ARG, "source and destination overlap");
+    if (src_dev && last > first && ((((uintptr_t)p) | ((uintptr_t)q)) & 7) != 0)
+      return fail(MSM_E_ARG, "device points not 8-byte aligned");
+  }
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  std::vector<uint8_t> own;  // nfail without is_one: counted from a buffer of our own
+  uint8_t *st = is_one;
+  try {
+    if (!st && nfail) {
+      own.resize(k);
+      st = own.data();
+    }
+    std::vector<size_t> single;  // offsets == NULL: one pair per segment
+    if (!fe_only && !offsets) {
+      single.resize(k + 1);
+      for (size_t i = 0; i <= k; ++i) single[i] = i;
+      offsets = single.data();
+    }
+    bulk_run<Pairing>(dev, 0, src_dev, dst_dev, user, [&](Pairing &e, hipStream_t cs) {
+      if (fe_only) e.run_final_exp(cs, src, k, dst, st, src_dev, dst_dev);
+      else e.run(cs, p, q, offsets, k, dst, st, fe, src_dev, dst_dev);
+    });
+    if (nfail) *nfail = k - (size_t)std::count(st, st + k, (uint8_t)1);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (dst && !dst_dev) memset(dst, 0, k * GT);  // never half written
+    if (is_one) memset(is_one, 0, k);
+    if (nfail) *nfail = k;
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   size_t w = 0;
   while (n >>= 1) ++w;
@@ -1035,6 +1098,21 @@ int msm_h2c_dst_prime(byte *out, size_t *out_len, const byte *DST, size_t DST_le
   *out_len = h2c_dst_prime(out, DST, DST_len);
   return MSM_OK;
 }
+
+int msm_pairing_segments(int device, void *dst_fp12, uint8_t *is_one, size_t *nfail, const void *p_affine,
+                         const void *q_affine, const size_t *offsets, size_t nsegments, int flags, int src_on_device,
+                         int dst_on_device, void *hip_stream) {
+  return pairing_checked(device, dst_fp12, is_one, nfail, p_affine, q_affine, nullptr, offsets, nsegments, flags, false,
+                         src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_fp12_final_exp(int device, void *dst_fp12, uint8_t *is_one, size_t *nfail, const void *src_fp12, size_t n,
+                       int src_on_device, int dst_on_device, void *hip_stream) {
+  return pairing_checked(device, dst_fp12, is_one, nfail, nullptr, nullptr, src_fp12, nullptr, n, 0, true,
+                         src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+size_t msm_pairing_piece(size_t npairs) { return pair_piece_len(std::min(std::max(npairs, (size_t)1), pair_chunk())); }
 
 const char *msm_last_error(void) { return g_err.c_str(); }
 
