@@ -91,8 +91,19 @@ MSM_FN void xyzz_dbl(Xyzz<F> &r, const Xyzz<F> &a) {
 
 // acc += (neg ? -P : P); P affine, canonical, not infinity (callers skip the
 // all-zero affine point, as ec_ops.h:717 does).
+// acc_affine: acc is exactly what xyzz_from_aff left (ZZ1 = ZZZ1 = 1, a
+// bucket's first entry), so the four products by one are skipped: U2 := X2,
+// S2 := +-Y2, ZZ3 := PP, ZZZ3 := PPP -- 5 reductions instead of 9 for every
+// bucket's first add.  The flag may differ between the lanes of a wave (it
+// must not differ inside a G2 lane pair; a pair shares its bucket); the skips
+// are branches around the products of the one madd body, not a second copy of
+// it.  A negated Y2 is reduced as xyzz_from_aff reduces it: the generic path
+// reduces it in the product S2 = Y2 ZZZ1, and left lazy (< 4p) it would put R
+// at 8p, past the < 6p f_sqr and f_mul_sub are proven for
+// (tests/test_first_pair_bounds.py).  X2 and +-Y2 are in class S like the
+// products they replace, so every later range is the generic path's.
 template <class F>
-MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg) {
+MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg, bool acc_affine = false) {
   if (xyzz_is_inf(acc)) {
     xyzz_from_aff(acc, p, neg);
     return;
@@ -103,8 +114,14 @@ MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg) {
   } else {
     y2 = p.y;
   }
-  f_mul_bs(P, p.x, acc.zz);   // U2 = X2 ZZ1          S
-  f_mul_bs(R, y2, acc.zzz);   // S2 = Y2 ZZZ1         S
+  if (acc_affine) {
+    P = p.x;                    // U2 = X2              canonical
+    if (neg) f_nred(y2);        // S2 = +-Y2            S
+    R = y2;
+  } else {
+    f_mul_bs(P, p.x, acc.zz);   // U2 = X2 ZZ1          S
+    f_mul_bs(R, y2, acc.zzz);   // S2 = Y2 ZZZ1         S
+  }
   f_sub16(P, P, acc.x);    // P = U2 - X1          < 18p lazy
   f_sub4(R, R, acc.y);     // R = S2 - Y1          < 6p lazy
   f_sqr(PP, P);            // PP                   S
@@ -126,10 +143,21 @@ MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg) {
   // ordered so that ZZ1, P, X1 and PP die as early as possible (register
   // pressure: 8-10 live field elements; G2 elements are 28 VGPRs each);
   // f_mul_bs: second operand normalized (every S value here)
-  f_mul_bs(acc.zz, acc.zz, PP);    // ZZ3 = ZZ1 PP         S
+  // (only where the flag is a run-time value: every other caller's madd
+  // compiles to what it was)
+  if (!__builtin_constant_p(acc_affine)) f_pin(PP);
+  if (acc_affine) {
+    acc.zz = PP;                     // ZZ3 = PP             S
+  } else {
+    f_mul_bs(acc.zz, acc.zz, PP);    // ZZ3 = ZZ1 PP         S
+  }
   f_mul_bs(PPP, P, PP);         // S
   f_mul_bs(acc.x, acc.x, PP);      // Q = X1 PP  (in place of X1)   S
-  f_mul_bs(acc.zzz, acc.zzz, PPP); // ZZZ3 = ZZZ1 PPP      S
+  if (acc_affine) {
+    acc.zzz = PPP;                   // ZZZ3 = PPP           S
+  } else {
+    f_mul_bs(acc.zzz, acc.zzz, PPP); // ZZZ3 = ZZZ1 PPP      S
+  }
   F X3;
   f_sqr(X3, R);            // R^2                  S
   f_sub_2x(X3, X3, PPP, acc.x);  // R^2 + 8p - PPP - 2Q   < 10p

@@ -445,6 +445,26 @@ MSM_FN void f_mul_bs(Fp2 &r, const Fp2 &a, const Fp2 &b) {
 }
 MSM_FN void f_mul_bs(Fp &r, const Fp &a, const Fp &b) { fp_mul(r, a, b); }
 
+// f_pin: the limbs of a stay the 32-bit registers they are, whatever the value
+// is merged with afterwards (no instruction; nothing in the host build).  A
+// product's limbs are (uint32_t)acc & MASK of a 64-bit column; where such a value
+// also becomes a coordinate on one side of a branch (xyzz_madd's first-add
+// skips, ec.hpp) the compiler carried its low 13 limbs as 64-bit values into the
+// next products and multiplied both halves: 574 instead of 392 mads per product
+// and ~380 moves (profiles/acc_first_pair_isa.txt).
+MSM_FN void f_pin(Fp &a) {
+#ifndef MSM_FP_HOST_TEST
+#pragma unroll
+  for (int i = 0; i < NL; ++i) asm volatile("" : "+v"(a.v[i]));
+#else
+  (void)a;
+#endif
+}
+MSM_FN void f_pin(Fp2 &a) {
+  f_pin(a.c0);
+  f_pin(a.c1);
+}
+
 // (a0 + a1 i)^2 = (a0+a1)(a0-a1) + 2 a0 a1 i   (ref no_asm.h:638-688)
 // Both components are normalized first: with lazy inputs (limbs < 3 2^28) the
 // product s d would reach 14 (6 2^28)(5 2^28) > 2^64 in a column (DESIGN 4a,

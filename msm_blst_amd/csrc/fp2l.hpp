@@ -106,6 +106,7 @@ MSM_FN bool f_is_zero_S(const Fp2L &a) {
   return (z & pair_swap(z)) != 0;
 }
 MSM_FN void f_mul3(Fp2L &r, const Fp2L &a) { f_mul3(r.c, a.c); }
+MSM_FN void f_pin(Fp2L &a) { f_pin(a.c); }
 // a b - c d (a lazy, b lazy normalized here, c, d in S), as f_mul_sub(Fp2):
 //   r0 = a0 b0 + a1 (8p - b1) + c0 (8p - d0) + c1 d1
 //   r1 = a1 b0 + a0 b1 + c1 (8p - d0) + c0 (8p - d1)

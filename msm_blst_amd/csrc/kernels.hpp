@@ -315,6 +315,12 @@ __device__ __forceinline__ void accumulate_bucket(const AccSched &S, const PT *_
   const PayloadStream ps(S, (uint32_t)t);
   Xyzz<F> acc;
   xyzz_set_inf(acc);
+  // fresh: acc is exactly xyzz_from_aff of the previous entry (this madd found
+  // the bucket at infinity and started it), so the next madd is the bucket's
+  // first add and skips its four products by ZZ1 = ZZZ1 = 1 (ec.hpp).  Per lane:
+  // the schedule orders buckets by entry count, so the flag is wave-uniform
+  // except where the rare branches (infinity rows, P == -bucket) restart a bucket.
+  bool fresh = false;
 #if MSM_ACC_PREFETCH == 2
   // A/B knob (build time): the next entry's x loaded before this entry's madd,
   // this entry's y at the top of its iteration (first used by the madd's second
@@ -332,7 +338,9 @@ __device__ __forceinline__ void accumulate_bucket(const AccSched &S, const PT *_
       nx = ld_coord(&pts[e & 0x7fffffffu], 0);
     }
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
-    xyzz_madd(acc, p, (ce >> 31) != 0);
+    const bool start = xyzz_is_inf(acc);
+    xyzz_madd(acc, p, (ce >> 31) != 0, fresh);
+    fresh = start;
   }
 #elif MSM_ACC_PREFETCH
   // A/B knob (build time): the next entry's row loaded before this entry's madd
@@ -347,14 +355,18 @@ __device__ __forceinline__ void accumulate_bucket(const AccSched &S, const PT *_
       nxt = ld_point(&pts[e & 0x7fffffffu]);
     }
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
-    xyzz_madd(acc, p, (ce >> 31) != 0);
+    const bool start = xyzz_is_inf(acc);
+    xyzz_madd(acc, p, (ce >> 31) != 0, fresh);
+    fresh = start;
   }
 #else
   for (uint32_t k = 0; k < cnt; ++k) {
     const uint32_t e = ps.at(k);
     Aff<F> p = ld_point(&pts[e & 0x7fffffffu]);
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
-    xyzz_madd(acc, p, (e >> 31) != 0);
+    const bool start = xyzz_is_inf(acc);
+    xyzz_madd(acc, p, (e >> 31) != 0, fresh);
+    fresh = start;
   }
 #endif
   st16(&buckets[S.order[t]], acc);

@@ -157,6 +157,9 @@ __device__ __forceinline__ void accumulate_pair(const AccSched &S, const PT *__r
   const PayloadStream ps(S, pos);
   Xyzz<Fp2L> acc;
   xyzz_set_inf(acc);
+  // the next madd is the bucket's first add (accumulate_bucket, kernels.hpp);
+  // both lanes of a pair hold the same bucket, so the flag is pair-uniform
+  bool fresh = false;
 #if MSM_ACC2P_PREFETCH
   // the next entry's row is loaded before this entry's madd (28 VGPRs of the
   // 256 a 2-wave kernel has), so its HBM latency hides behind the madd's issue
@@ -171,7 +174,9 @@ __device__ __forceinline__ void accumulate_pair(const AccSched &S, const PT *__r
       ld_point2l(nxt, &pts[e & 0x7fffffffu], comp);
     }
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
-    xyzz_madd(acc, p, (ce >> 31) != 0);
+    const bool start = xyzz_is_inf(acc);
+    xyzz_madd(acc, p, (ce >> 31) != 0, fresh);
+    fresh = start;
   }
 #else
   for (uint32_t k = 0; k < cnt; ++k) {
@@ -179,7 +184,9 @@ __device__ __forceinline__ void accumulate_pair(const AccSched &S, const PT *__r
     Aff<Fp2L> p;
     ld_point2l(p, &pts[e & 0x7fffffffu], comp);
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
-    xyzz_madd(acc, p, (e >> 31) != 0);
+    const bool start = xyzz_is_inf(acc);
+    xyzz_madd(acc, p, (e >> 31) != 0, fresh);
+    fresh = start;
   }
 #endif
   st_xyzz2l(&buckets[S.order[pos]], acc, comp);
