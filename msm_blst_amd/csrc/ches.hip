@@ -688,12 +688,21 @@ Ches<G>::~Ches() {
 }
 
 // bucket space = B plus (copies_ - 1) copies of the small buckets 1..small_;
-// copies_ is chosen so a copy receives ~12 top-digit entries (n / (small_ copies))
+// copies_ is chosen so a copy receives ~kTopCopyLen top-digit entries
+// (n / (small_ copies)).  Every copy is one more bucket, two general adds in
+// level 0 of the reduction; a longer copy is a longer accumulation lane.
+// MSM_TOP_COPY_LEN: A/B knob (12 / 24 / 32 measured: 12 is the fastest at 2^20
+// and at the 2^17 shard).
+constexpr int kTopCopyLen = 12;
 template <int G>
 void Ches<G>::plan_buckets(size_t n) {
+  static const size_t len = [] {
+    const char *e = getenv("MSM_TOP_COPY_LEN");
+    return (size_t)(e ? std::max(1, std::min(4096, atoi(e))) : kTopCopyLen);
+  }();
   int want = 1;
   if (small_ > 0 && n > 0) {
-    size_t c = (n + (size_t)small_ * 12 - 1) / ((size_t)small_ * 12);
+    size_t c = (n + (size_t)small_ * len - 1) / ((size_t)small_ * len);
     want = (int)std::min<size_t>(std::max<size_t>(c, 1), 256);
   }
   if (want == copies_ && red_.size()) return;

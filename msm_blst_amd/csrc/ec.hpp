@@ -167,14 +167,11 @@ MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg, bool acc_affine =
   acc.x = X3;
 }
 
-// acc += b, both xyzz in S
+// acc += b, both xyzz in S: the 13-reduction form (U1 = X1 ZZ2 and S1 = Y1 ZZZ2
+// reduced on their own).  Kept for the one-lane Fp2 and for hash_to_curve.hip,
+// see xyzz_add.
 template <class F>
-MSM_FN void xyzz_add(Xyzz<F> &acc, const Xyzz<F> &b) {
-  if (xyzz_is_inf(b)) return;
-  if (xyzz_is_inf(acc)) {
-    acc = b;
-    return;
-  }
+MSM_FN void xyzz_add_u1s1(Xyzz<F> &acc, const Xyzz<F> &b) {
   // Computed in place so that b dies early and at most ~8 field elements are
   // live (G2: 28 VGPRs each): acc is first rewritten as the representative
   // (U1, S1, ZZZ1 ZZZ2, ZZ1 ZZ2) of the same point, which is also what the
@@ -211,6 +208,81 @@ MSM_FN void xyzz_add(Xyzz<F> &acc, const Xyzz<F> &b) {
   f_sub16(t, acc.x, X3);
   f_mul_sub(acc.y, t, R, acc.y, PPP);  // Y3 = R (Q - X3) - S1 PPP   S (one reduction)
   acc.x = X3;
+}
+
+// Which fields take the regrouped add below.  The one-lane Fp2 does not: its
+// kernels sit at the 512 registers of a one-wave kernel, and with P and R as
+// four-product sums (fp_mul4: eight operands live at once) k_wbits_pairs<2>
+// spilled VGPRs, which no product kernel may (tests/test_kernel_resources.py;
+// DESIGN 11 has the history).  The range proof holds for it all the same
+// (tests/test_xyzz_add_bounds.py); none of these kernels is on a batch's
+// critical path.
+template <class F>
+struct AddRegrouped {
+  static constexpr bool value = true;
+};
+template <>
+struct AddRegrouped<Fp2> {
+  static constexpr bool value = false;
+};
+
+// the regrouped add of two finite points
+template <class F>
+MSM_FN void xyzz_add_regrouped(Xyzz<F> &acc, const Xyzz<F> &b) {
+  // 12 products and 2 squares with 11 Montgomery reductions instead of 13
+  // (DESIGN 23): U1 = X1 ZZ2 and S1 = Y1 ZZZ2 are never reduced on their own.
+  // P and R are each one two-product difference (f_mul_sub), and the later
+  // uses of U1 and S1 are regrouped around V = ZZ2 PP and W = ZZZ2 PPP, which
+  // ZZ3 and ZZZ3 need anyway:  Q = U1 PP = X1 V,  S1 PPP = Y1 W.
+  // Ordered so that b dies early (b.x, b.y in P and R, b.zz in V, b.zzz in W);
+  // at most nine field elements are live, at R (G2: 28 VGPRs each).
+  // f_mul_sub takes X1 and X2 in class X here (normalized, < 10p): a b + c
+  // (4p - d) < 10p 2p + 10p 4p = 60 p^2 and every column stays below 2^64
+  // (tests/test_xyzz_add_bounds.py).
+  F P, R, PP, PPP, V, W, t;
+  f_mul_sub_bs(P, b.x, acc.zz, acc.x, b.zz);    // P = X2 ZZ1 - X1 ZZ2     S
+  f_mul_sub_bs(R, b.y, acc.zzz, acc.y, b.zzz);  // R = Y2 ZZZ1 - Y1 ZZZ2   S
+  f_sqr(PP, P);                              // PP                      S
+  if (__builtin_expect(f_is_zero_S(PP), 0)) {
+    F RR;
+    f_sqr(RR, R);
+    if (f_is_zero_S(RR)) {
+      // b equals acc: double acc itself, which is still the untouched input
+      Xyzz<F> a = acc;
+      xyzz_dbl(acc, a);
+    } else {
+      xyzz_set_inf(acc);
+    }
+    return;
+  }
+  f_mul_bs(V, b.zz, PP);           // V = ZZ2 PP           S  (ZZ2 dies)
+  f_mul_bs(acc.zz, acc.zz, V);     // ZZ3 = ZZ1 V          S
+  f_mul_bs(acc.x, acc.x, V);       // Q = X1 V  (in place of X1)   S  (V dies)
+  f_mul_bs(PPP, P, PP);            // PPP                  S  (P, PP die)
+  f_mul_bs(W, b.zzz, PPP);         // W = ZZZ2 PPP         S  (ZZZ2 dies)
+  f_mul_bs(acc.zzz, acc.zzz, W);   // ZZZ3 = ZZZ1 W        S
+  F X3;
+  f_sqr(X3, R);
+  f_sub_2x(X3, X3, PPP, acc.x);
+  f_norm(X3);                   // X3 = R^2 - PPP - 2Q  X
+  f_sub16(t, acc.x, X3);
+  f_mul_sub_bs(acc.y, t, R, acc.y, W);  // Y3 = R (Q - X3) - Y1 W   S (one reduction; R is S here)
+  acc.x = X3;
+}
+
+// acc += b, both xyzz in S.  REGROUP = false asks for the 13-reduction form
+// (xyzz_add<F, false>(acc, b)): the cofactor-clearing kernel of
+// hash_to_curve.hip, two ladders and five adds in one body, lost a wave (G1) and
+// spilled (G2) with the regrouped one.
+template <class F, bool REGROUP = AddRegrouped<F>::value>
+MSM_FN void xyzz_add(Xyzz<F> &acc, const Xyzz<F> &b) {
+  if (xyzz_is_inf(b)) return;
+  if (xyzz_is_inf(acc)) {
+    acc = b;
+    return;
+  }
+  if constexpr (REGROUP) xyzz_add_regrouped(acc, b);
+  else xyzz_add_u1s1(acc, b);
 }
 
 }  // namespace msm

@@ -400,6 +400,9 @@ MSM_FN void f_mul_sub(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d)
   fp_neg<4>(nd, d);  // 4p - d, limbs < 2^29
   fp_mul2(r, a, b, c, nd);
 }
+// f_mul_sub for a b already normalized (class S, or any normalized value < 8p);
+// over Fp the same call
+MSM_FN void f_mul_sub_bs(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d) { f_mul_sub(r, a, b, c, d); }
 // 3a for a in S -> lazy (< 6p, limbs < 2^30)
 MSM_FN void f_mul3(Fp &r, const Fp &a) {
 #pragma unroll

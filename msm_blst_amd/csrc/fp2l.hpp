@@ -113,10 +113,11 @@ MSM_FN void f_pin(Fp2L &a) { f_pin(a.c); }
 // own operands first, partner second, the lane choice on the b / d side:
 //   even: a b + a' (8p - b') + c (8p - d) + c' d'
 //   odd:  a b' + a' b + c (8p - d') + c' (8p - d)
-MSM_FN void f_mul_sub(Fp2L &r, const Fp2L &a, const Fp2L &b, const Fp2L &c, const Fp2L &d) {
+template <bool BS>
+MSM_FN void f_mul_sub_impl(Fp2L &r, const Fp2L &a, const Fp2L &b, const Fp2L &c, const Fp2L &d) {
   const bool odd = pair_odd();
   Fp bn = b.c, pa, pb, pc, pd, nd, npb, Y1, Y2, Y3, Y4;
-  fp_norm(bn);
+  if (!BS) fp_norm(bn);
   pair_swap(pa, a.c);
   pair_swap(pb, bn);
   pair_swap(pc, c.c);
@@ -131,6 +132,13 @@ MSM_FN void f_mul_sub(Fp2L &r, const Fp2L &a, const Fp2L &b, const Fp2L &c, cons
   Fp t;
   fp_mul4(t, a.c, Y1, pa, Y2, c.c, Y3, pc, Y4);
   r.c = t;
+}
+MSM_FN void f_mul_sub(Fp2L &r, const Fp2L &a, const Fp2L &b, const Fp2L &c, const Fp2L &d) {
+  f_mul_sub_impl<false>(r, a, b, c, d);
+}
+// b already normalized (class S): no normalized copy of b beside b
+MSM_FN void f_mul_sub_bs(Fp2L &r, const Fp2L &a, const Fp2L &b, const Fp2L &c, const Fp2L &d) {
+  f_mul_sub_impl<true>(r, a, b, c, d);
 }
 
 }  // namespace msm

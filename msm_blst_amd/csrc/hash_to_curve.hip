@@ -434,6 +434,15 @@ static __global__ void __launch_bounds__(128)
 // ------------------------------------------------------------ cofactor ----
 constexpr uint64_t H2C_Z_ABS = DEC_Z_ABS;  // the curve parameter is -|z|
 
+// The general add of the clearing kernel: the 13-reduction form (ec.hpp
+// xyzz_add).  k_h2c_clear holds two ladders and five adds in one body; with the
+// regrouped add it went from 246 to 301 registers (G1, two waves to one) and
+// spilled (G2).
+template <class F>
+__device__ __forceinline__ void h2c_add(Xyzz<F> &acc, const Xyzz<F> &b) {
+  xyzz_add<F, false>(acc, b);
+}
+
 // acc = [k] base for a constant k with bit 63 set; acc enters as base
 template <class F>
 __device__ __forceinline__ void h2c_times(Xyzz<F> &acc, const Xyzz<F> &base, uint64_t k) {
@@ -441,7 +450,7 @@ __device__ __forceinline__ void h2c_times(Xyzz<F> &acc, const Xyzz<F> &base, uin
   for (int b = 62; b >= 0; --b) {
     const Xyzz<F> tmp = acc;
     xyzz_dbl(acc, tmp);
-    if ((k >> b) & 1) xyzz_add(acc, base);  // uniform: k is a constant
+    if ((k >> b) & 1) h2c_add(acc, base);  // uniform: k is a constant
   }
 }
 template <class F>
@@ -495,9 +504,9 @@ static __global__ void __launch_bounds__(128)
     h2c_psi(A);
     h2c_psi(A);
     h2c_negate(A);
-    xyzz_add(A, P);
+    h2c_add(A, P);
     h2c_psi(P);
-    xyzz_add(A, P);
+    h2c_add(A, P);
     h2c_negate(A);
     f_nred(A.x);
     pm_st_xyzz(park, A, comp);
@@ -505,15 +514,15 @@ static __global__ void __launch_bounds__(128)
     pm_ld_xyzz(P, &pts[t], comp);
     A = P;
     h2c_times(A, P, H2C_Z_ABS);
-    xyzz_add(A, P);
+    h2c_add(A, P);
     h2c_psi(P);
     h2c_negate(P);
-    xyzz_add(A, P);
+    h2c_add(A, P);
     // [-z] t0 = [z^2 - z]P + [z]Psi(P), plus the parked sum
     P = A;
     h2c_times(A, P, H2C_Z_ABS);
     pm_ld_xyzz(P, park, comp);
-    xyzz_add(A, P);
+    h2c_add(A, P);
   }
   pm_st_xyzz(&pts[t], A, comp);
 }

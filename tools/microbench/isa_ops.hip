@@ -55,3 +55,16 @@ __global__ void __launch_bounds__(256) k_op_g2l_madd(const Xyzz<Fp2L> *acc, cons
   xyzz_madd(q, p[t], (t & 2) != 0);
   r[t] = q;
 }
+// the general add of the reductions (k_segsum and the rest), G1 and G2 lane pair
+__global__ void __launch_bounds__(256, 3) k_op_g1_add(const Xyzz<Fp> *acc, const Xyzz<Fp> *b, Xyzz<Fp> *r) {
+  const int t = threadIdx.x;
+  Xyzz<Fp> q = acc[t];
+  xyzz_add(q, b[t]);
+  r[t] = q;
+}
+__global__ void __launch_bounds__(256) k_op_g2l_add(const Xyzz<Fp2L> *acc, const Xyzz<Fp2L> *b, Xyzz<Fp2L> *r) {
+  const int t = threadIdx.x;
+  Xyzz<Fp2L> q = acc[t];
+  xyzz_add(q, b[t]);
+  r[t] = q;
+}
