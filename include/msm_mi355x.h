@@ -649,6 +649,111 @@ int msm_fp12_final_exp(int device, void *dst_fp12, uint8_t *is_one, size_t *nfai
  * MSM_PAIRING_CHUNK as set at the call) */
 size_t msm_pairing_piece(size_t npairs);
 
+/* ---- bulk BLS signature verification (replaces a host loop over the reference's
+ * blst_core_verify_pk_in_g{1,2} and its blst_pairing_chk_n_aggr_pk_in_g{1,2} /
+ * blst_pairing_chk_n_mul_n_aggr_pk_in_g{1,2} / blst_pairing_commit /
+ * blst_pairing_finalverify sequences: ref src/aggregate.c:98-339, 390-501, 625-673) ----
+ * scheme is the group of the public keys: MSM_SIG_MIN_PK keys in G1, signatures and
+ * hashes in G2 (the reference's *_pk_in_g1 calls); MSM_SIG_MIN_SIG keys in G2,
+ * signatures and hashes in G1 (*_pk_in_g2).  Every check decides
+ *   e(-g, S) prod_i e(PK'_i, H(m_i)) == 1        (min-sig: the sides swapped)
+ * with g the generator of the keys' group.  status[j] is a BLST_ERROR value, one byte
+ * per check: 0 success, 1 bad encoding, 2 not on curve, 3 not in group, 5 verify fail,
+ * 6 public key is infinity.  status and nfail are HOST memory (either may be NULL, not
+ * both); *nfail = the number of non-zero statuses; a call returns once they are written.
+ * Keys, signatures, msgs, aug and scalars share one memory space (src_on_device);
+ * every offsets array and DST are HOST memory.  msgs / msg_offsets / msg_len / aug /
+ * aug_len / DST and the flag MSM_H2C_ENCODE are exactly those of msm_points_hash
+ * (message i of the call belongs to tuple i).  With MSM_SIG_ENCODED keys and signatures
+ * are compressed ZCash entries (48 bytes in G1, 96 in G2); without it blst affine
+ * points (96 / 192 bytes, infinity all zero) that are ASSUMED to lie on the curve, as
+ * the reference assumes it.
+ *
+ * msm_sigs_verify: nchecks independent checks; check i has message i, signature i and
+ *   the keys pk_offsets[i] .. pk_offsets[i + 1] (pk_offsets NULL: key i alone), which
+ *   are summed (FastAggregateVerify); with one key it is blst_core_verify_pk_in_g{1,2}.
+ * msm_sigs_aggregate_verify: check j has signature j and the (key, message) tuples
+ *   offsets[j] .. offsets[j + 1]: blst_pairing_chk_n_aggr_pk_in_g{1,2} per tuple with
+ *   both group checks on and the signature passed with the first tuple, then
+ *   blst_pairing_commit and blst_pairing_finalverify(ctx, NULL).  Messages are not
+ *   required to be distinct (nor does the reference require it).
+ * msm_sigs_batch_verify: check j has the (key, message, signature, scalar) tuples
+ *   offsets[j] .. offsets[j + 1]: blst_pairing_chk_n_mul_n_aggr_pk_in_g{1,2} per tuple,
+ *   then commit and finalverify.  Scalar i is the low nbits bits of the little-endian
+ *   value at scalars + i scalar_stride, with the rules of msm_points_mult; it multiplies
+ *   signature i and the G1 side of tuple i (the key in min-pk, the hash in min-sig, as
+ *   the reference).  scalars NULL or nbits == 0: the unweighted form.  The caller
+ *   supplies the weights, as blst's caller does: they MUST be unpredictable to the
+ *   signers (fresh randomness of at least 64 bits per tuple, non-zero), or a batch of
+ *   forged signatures can be made to pass.
+ * Tuples (keys, messages, signatures, scalars) are indexed from 0; those below
+ * offsets[0] are ignored.
+ *
+ * The status of a check is the code of the FIRST failing step of this sequence.  Per
+ * tuple, in order (msm_sigs_verify and msm_sigs_aggregate_verify have one signature,
+ * taken with the first tuple):
+ *   the signature: with MSM_SIG_ENCODED its uncompress code (1, 2); an infinite
+ *     signature is skipped, not rejected; otherwise 3 when it lies outside its group;
+ *   then each key of the tuple, in order: its uncompress code; 6 when it is infinite;
+ *     3 when it lies outside its group.
+ * msm_sigs_verify then gives 6 when the sum of the keys is infinite (an empty set
+ * included).  When no step fails: 0 when the pairing product is one, else 5.  A check
+ * of the aggregate and batch calls with no tuples gives 5 (the reference's finalverify
+ * returns 0 when nothing was aggregated).  One difference, on inputs no honest caller
+ * produces: where the signatures of a check sum to infinity, or a weighted point is
+ * infinity, the pair is left out of the product (factor one).
+ *
+ * nchecks == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: NULL
+ * status and nfail, a NULL array that is read, a decreasing offset, unknown scheme or
+ * flag bits, nbits > 256, a scalar_stride shorter than (nbits + 7) / 8 or above 2^20,
+ * misaligned device points (8 bytes; encoded entries 4).  MSM_E_NODEV: no such device.
+ * MSM_E_HIP: a HIP failure; every status is then 5 and *nfail the number of checks.
+ * Streams as msm_points_to_affine.  On the GPU: csrc/sig_verify.hip (DESIGN section
+ * 24): the decode, screen, sum, mult, hash and pairing engines on one stream, the
+ * intermediates in device memory; chunks of whole checks of at most 2^16 tuples
+ * (MSM_SIGS_CHUNK=<tuples> overrides, read at each call; a longer check is a chunk of
+ * its own).  Thread-safe per call (an engine pool keyed by (device, scheme), counted
+ * by msm_engine_cache_stats(), freed by msm_release_engine_cache()).
+ *
+ * msm_points_in_group: in_group[i] = blst_p{1,2}_affine_in_g{1,2}(P_i) for npoints blst
+ * affine points in host or device memory; infinity passes; the points are not
+ * modified; in_group is HOST memory.  Errors as above (a HIP failure fills in_group
+ * with 0); the pool is keyed by (device, group). */
+enum { MSM_SIG_MIN_PK = 1, MSM_SIG_MIN_SIG = 2 }; /* scheme */
+enum { MSM_SIG_ENCODED = 2 };                     /* flags, beside MSM_H2C_ENCODE */
+int msm_sigs_verify(int scheme, int device, uint8_t *status, size_t *nfail, const void *pks, const size_t *pk_offsets,
+                    const void *sigs, const void *msgs, const size_t *msg_offsets, size_t msg_len, const void *aug,
+                    size_t aug_len, size_t nchecks, const byte *DST, size_t DST_len, int flags, int src_on_device,
+                    void *hip_stream);
+int msm_sigs_aggregate_verify(int scheme, int device, uint8_t *status, size_t *nfail, const void *pks, const void *sigs,
+                              const void *msgs, const size_t *msg_offsets, size_t msg_len, const void *aug,
+                              size_t aug_len, const size_t *offsets, size_t nchecks, const byte *DST, size_t DST_len,
+                              int flags, int src_on_device, void *hip_stream);
+int msm_sigs_batch_verify(int scheme, int device, uint8_t *status, size_t *nfail, const void *pks, const void *sigs,
+                          const byte *scalars, size_t nbits, size_t scalar_stride, const void *msgs,
+                          const size_t *msg_offsets, size_t msg_len, const void *aug, size_t aug_len,
+                          const size_t *offsets, size_t nchecks, const byte *DST, size_t DST_len, int flags,
+                          int src_on_device, void *hip_stream);
+int msm_points_in_group(int group, int device, uint8_t *in_group, const void *points_affine, size_t npoints,
+                        int src_on_device, void *hip_stream);
+/* host only, no device work.  msm_sigs_chunk: the tuples per chunk as set at the call.
+ * msm_sigs_plan: the chunk of whole checks that starts at check c0 under `chunk` tuples
+ * (mode 0 verify, 1 aggregate, 2 batch): *c1 its end, counts = {message rows, keys,
+ * signatures, pairing rows}; per pairing row its check (relative to c0) and source (the
+ * row's index in the chunk, 0x80000000 the check's signature row); the pairing offsets
+ * and, where the mode has them, the segment offsets of the key sums and the signature
+ * sums (each checks + 1 values).  Arrays may be NULL; at most `capacity` values are
+ * written to each.  msm_sigs_reduce: the statuses of the checks [c0, c1) from the
+ * screen's code bytes of their signatures and keys (0, 1, 2, 3, 0x80 infinity), the
+ * late bytes (1: the key sum is infinite; may be NULL) and the pairing verdicts. */
+size_t msm_sigs_chunk(void);
+int msm_sigs_plan(int mode, const size_t *offsets, const size_t *pk_offsets, size_t nchecks, size_t c0, size_t chunk,
+                  size_t *c1, size_t counts[4], uint32_t *ent_check, uint32_t *ent_src, size_t *pair_off,
+                  size_t *key_off, size_t *sig_off, size_t capacity);
+int msm_sigs_reduce(int mode, const size_t *offsets, const size_t *pk_offsets, size_t c0, size_t c1,
+                    const uint8_t *sig_codes, const uint8_t *key_codes, const uint8_t *late, const uint8_t *is_one,
+                    uint8_t *status);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

@@ -26,6 +26,9 @@ Mirrors:
                                                       hash_to_field.c:51-154), bulk, on the GPU
   ps_pairing, ps_pairing_segments, ps_pairing_check,  blst_miller_loop / blst_fp12_mul / blst_final_exp / blst_fp12_is_one
   ps_final_exp                                        (ref pairing.c:181-262, 371-404), bulk, on the GPU
+  ps_verify, ps_aggregate_verify, ps_batch_verify,    blst_core_verify_pk_in_g{1,2} and the blst_pairing_chk_n_[mul_n_]aggr_pk_in_g{1,2}
+  ps_in_group                                         / commit / finalverify sequences (ref aggregate.c), blst_p{1,2}_affine_in_g{1,2},
+                                                      bulk, on the GPU
 """
 import ctypes
 
@@ -39,6 +42,8 @@ __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext
            "ps_msm_segments", "ps_sum_segments", "segments_plan",
            "ps_map_to_curve", "ps_hash_to_field", "ps_hash_to_curve", "h2c_dst_prime",
            "ps_pairing", "ps_pairing_segments", "ps_pairing_check", "ps_final_exp", "fp12_one", "FP12_BYTES",
+           "ps_verify", "ps_aggregate_verify", "ps_batch_verify", "ps_in_group", "sigs_plan", "sigs_reduce",
+           "SIG_MIN_PK", "SIG_MIN_SIG",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -50,6 +55,8 @@ SRC_AFFINE, SRC_JACOBIAN = 0, 1        # MSM_SRC_*: 96 G / 144 G bytes per point
 H2C_ENCODE = 1                         # MSM_H2C_ENCODE
 PAIRING_MILLER_ONLY = 1                # MSM_PAIRING_MILLER_ONLY
 FP12_BYTES = 576                       # a GT value: blst_fp12
+SIG_MIN_PK, SIG_MIN_SIG = 1, 2         # MSM_SIG_*: the group of the public keys
+SIG_ENCODED = 2                        # MSM_SIG_ENCODED
 
 
 def device_count():
@@ -552,6 +559,165 @@ def ps_final_exp(f, n, *, src_on_device=False, dst=None, device=0, stream=None):
     out = (ctypes.c_uint8 * (FP12_BYTES * n))()
     check(lib().msm_fp12_final_exp(device, out, None, None, src, n, sd, 0, stream))
     return bytes(out)
+
+
+def _sig_points(what, data, n, size, on_device):
+    if on_device:
+        return data
+    if n == 0:
+        return None
+    b = _buf(data)
+    have = len(b) if hasattr(b, "__len__") else ctypes.sizeof(b)
+    if have < n * size:
+        raise ValueError(f"{have} bytes of {what} given, {n * size} needed")
+    return b
+
+
+def _check_offsets(what, offsets):
+    offs = [int(v) for v in offsets]
+    if not offs:
+        raise ValueError(f"{what} must hold nchecks + 1 values")
+    if offs[0] < 0 or any(b < a for a, b in zip(offs, offs[1:])):
+        raise ValueError(f"{what} must be non-negative and non-decreasing")
+    return offs
+
+
+def _sigs(mode, scheme, pks, sigs, msgs, check_offsets, pk_offsets, scalars, nbits, stride, dst_tag, offsets, msg_len,
+          n, aug, aug_len, encode, encoded, src_on_device, device, stream):
+    if scheme not in (SIG_MIN_PK, SIG_MIN_SIG):
+        raise ValueError("scheme must be SIG_MIN_PK (1) or SIG_MIN_SIG (2)")
+    kg, sg = scheme, 3 - scheme
+    nmsg, src, o, ml, a, al = _h2c_messages(sg, msgs, offsets, msg_len, aug, aug_len, src_on_device, n)
+    ksz = (48 if encoded else 96) * kg
+    ssz = (48 if encoded else 96) * sg
+    if mode == 0:
+        k, co, nsig = nmsg, None, nmsg
+        if pk_offsets is not None:
+            po = _check_offsets("pk_offsets", pk_offsets)
+            if len(po) != k + 1:
+                raise ValueError(f"pk_offsets holds {len(po)} values for {k} messages")
+            nkeys, pko = po[-1], (ctypes.c_size_t * len(po))(*po)
+        else:
+            nkeys, pko = k, None
+    else:
+        co = _check_offsets("check_offsets", check_offsets)
+        k = len(co) - 1
+        if co[-1] > nmsg:
+            raise ValueError(f"check_offsets ends at {co[-1]} with {nmsg} messages")
+        nkeys, nsig, pko = co[-1], (k if mode == 1 else co[-1]), None
+    kb = _sig_points("public keys", pks, nkeys, ksz, src_on_device)
+    sb = _sig_points("signatures", sigs, nsig, ssz, src_on_device)
+    flags = (H2C_ENCODE if encode else 0) | (SIG_ENCODED if encoded else 0)
+    tag = bytes(dst_tag)
+    sd = int(bool(src_on_device))
+    status = (ctypes.c_uint8 * max(k, 1))()
+    nfail = ctypes.c_size_t(0)
+    L = lib()
+    if mode == 0:
+        check(L.msm_sigs_verify(scheme, device, status, ctypes.byref(nfail), kb, pko, sb, src, o, ml, a, al, k, tag,
+                                len(tag), flags, sd, stream))
+    else:
+        cof = (ctypes.c_size_t * len(co))(*co)
+        if mode == 1:
+            check(L.msm_sigs_aggregate_verify(scheme, device, status, ctypes.byref(nfail), kb, sb, src, o, ml, a, al,
+                                              cof, k, tag, len(tag), flags, sd, stream))
+        else:
+            nbits = int(nbits)
+            if nbits < 0 or nbits > 256:
+                raise ValueError("nbits must be in 0 .. 256")
+            nb = (nbits + 7) // 8
+            stride = nb if stride is None else int(stride)
+            if scalars is not None and stride < nb:
+                raise ValueError("stride shorter than (nbits + 7) / 8")
+            wb = None
+            if scalars is not None:
+                wb = scalars if src_on_device else _sig_points("scalars", scalars, 1, max((co[-1] - 1) * stride + nb, 0),
+                                                               False) if co[-1] else None
+            check(L.msm_sigs_batch_verify(scheme, device, status, ctypes.byref(nfail), kb, sb, wb, nbits, stride, src,
+                                          o, ml, a, al, cof, k, tag, len(tag), flags, sd, stream))
+    out = bytes(status[:k])
+    assert nfail.value == sum(1 for v in out if v)
+    return out
+
+
+def ps_verify(scheme, pks, sigs, msgs, *, dst_tag, pk_offsets=None, offsets=None, msg_len=None, n=None, aug=None,
+              aug_len=0, encode=False, encoded=False, src_on_device=False, device=0, stream=None):
+    """One status byte per signature (msm_sigs_verify): check i verifies signature i over
+    message i under the sum of the keys pk_offsets[i] .. pk_offsets[i + 1] (without
+    pk_offsets: key i), as blst_core_verify_pk_in_g{1,2} does.  scheme: SIG_MIN_PK (keys in
+    G1) or SIG_MIN_SIG (keys in G2).  Status: 0 success, 1 bad encoding, 2 not on curve,
+    3 not in group, 5 verify fail, 6 public key is infinity.  pks / sigs: blst affine
+    points, or with encoded compressed ZCash entries; messages, offsets, aug, dst_tag and
+    encode as in ps_hash_to_curve; everything in host memory, or with src_on_device
+    device pointers."""
+    return _sigs(0, scheme, pks, sigs, msgs, None, pk_offsets, None, 0, None, dst_tag, offsets, msg_len, n, aug,
+                 aug_len, encode, encoded, src_on_device, device, stream)
+
+
+def ps_aggregate_verify(scheme, pks, sigs, msgs, check_offsets, *, dst_tag, offsets=None, msg_len=None, n=None,
+                        aug=None, aug_len=0, encode=False, encoded=False, src_on_device=False, device=0, stream=None):
+    """One status byte per aggregate signature (msm_sigs_aggregate_verify): check j verifies
+    signature j over the (key, message) tuples check_offsets[j] .. check_offsets[j + 1], the
+    reference's blst_pairing_chk_n_aggr_pk_in_g{1,2} / commit / finalverify sequence.  The
+    other arguments and the statuses as in ps_verify."""
+    return _sigs(1, scheme, pks, sigs, msgs, check_offsets, None, None, 0, None, dst_tag, offsets, msg_len, n, aug,
+                 aug_len, encode, encoded, src_on_device, device, stream)
+
+
+def ps_batch_verify(scheme, pks, sigs, msgs, check_offsets, *, dst_tag, scalars=None, nbits=64, stride=None,
+                    offsets=None, msg_len=None, n=None, aug=None, aug_len=0, encode=False, encoded=False,
+                    src_on_device=False, device=0, stream=None):
+    """One status byte per batch (msm_sigs_batch_verify): check j verifies the (key, message,
+    signature, scalar) tuples check_offsets[j] .. check_offsets[j + 1] with one final
+    exponentiation, the reference's blst_pairing_chk_n_mul_n_aggr_pk_in_g{1,2} / commit /
+    finalverify sequence.  scalars: the weights, nbits bits each, stride (default (nbits +
+    7) // 8) bytes apart, little-endian; they must be unpredictable to the signers.
+    scalars=None or nbits=0: the unweighted form.  The other arguments and the statuses as
+    in ps_verify."""
+    return _sigs(2, scheme, pks, sigs, msgs, check_offsets, None, scalars, nbits, stride, dst_tag, offsets, msg_len, n,
+                 aug, aug_len, encode, encoded, src_on_device, device, stream)
+
+
+def ps_in_group(group, points, n, *, src_on_device=False, device=0, stream=None):
+    """n bytes, 1 where affine point i lies in the prime-order subgroup (msm_points_in_group:
+    blst_p{1,2}_affine_in_g{1,2}; infinity passes).  The points are not modified."""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    src = _sig_points("points", points, n, POINT_BYTES[group], src_on_device)
+    out = (ctypes.c_uint8 * max(n, 1))()
+    check(lib().msm_points_in_group(group, device, out, src, n, int(bool(src_on_device)), stream))
+    return bytes(out[:n])
+
+
+def sigs_plan(mode, check_offsets, pk_offsets, nchecks, c0, chunk):
+    """The chunk of checks that starts at c0 (msm_sigs_plan; host only): a dict with c1,
+    rows, keys, sigs, ent (list of (check, source)), pair_off, key_off, sig_off."""
+    co = (ctypes.c_size_t * len(check_offsets))(*check_offsets) if check_offsets is not None else None
+    po = (ctypes.c_size_t * len(pk_offsets))(*pk_offsets) if pk_offsets is not None else None
+    c1 = ctypes.c_size_t(0)
+    counts = (ctypes.c_size_t * 4)()
+    check(lib().msm_sigs_plan(mode, co, po, nchecks, c0, chunk, ctypes.byref(c1), counts, None, None, None, None, None, 0))
+    nent, nc = counts[3], c1.value - c0
+    cap = max(nent, nc + 1)
+    ec, es = (ctypes.c_uint32 * cap)(), (ctypes.c_uint32 * cap)()
+    pf, kf, sf = (ctypes.c_size_t * cap)(), (ctypes.c_size_t * cap)(), (ctypes.c_size_t * cap)()
+    check(lib().msm_sigs_plan(mode, co, po, nchecks, c0, chunk, ctypes.byref(c1), counts, ec, es, pf, kf, sf, cap))
+    return {"c1": c1.value, "rows": counts[0], "keys": counts[1], "sigs": counts[2],
+            "ent": [(ec[i], es[i]) for i in range(nent)], "pair_off": list(pf[:nc + 1]),
+            "key_off": list(kf[:nc + 1]) if mode == 0 and po is not None else [],
+            "sig_off": list(sf[:nc + 1]) if mode == 2 else []}
+
+
+def sigs_reduce(mode, check_offsets, pk_offsets, c0, c1, sig_codes, key_codes, late, is_one):
+    """The statuses of the checks [c0, c1) from the screen's codes (msm_sigs_reduce; host only)."""
+    co = (ctypes.c_size_t * len(check_offsets))(*check_offsets) if check_offsets is not None else None
+    po = (ctypes.c_size_t * len(pk_offsets))(*pk_offsets) if pk_offsets is not None else None
+    out = (ctypes.c_uint8 * max(c1 - c0, 1))()
+    check(lib().msm_sigs_reduce(mode, co, po, c0, c1, bytes(sig_codes) + b"\0", bytes(key_codes) + b"\0",
+                                bytes(late) if late is not None else None, bytes(is_one) + b"\0", out))
+    return bytes(out[:c1 - c0])
 
 
 def to_affine_levels(n):

@@ -143,6 +143,15 @@ def lib():
     L.msm_fp12_final_exp.argtypes = [i32, vp, vp, vp, vp, sz, i32, i32, vp]
     L.msm_pairing_piece.argtypes = [sz]
     L.msm_pairing_piece.restype = sz
+    L.msm_sigs_verify.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, i32, vp]
+    L.msm_sigs_aggregate_verify.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, i32, i32, vp]
+    L.msm_sigs_batch_verify.argtypes = [i32, i32, vp, vp, vp, vp, vp, sz, sz, vp, vp, sz, vp, sz, vp, sz, vp, sz, i32,
+                                        i32, vp]
+    L.msm_points_in_group.argtypes = [i32, i32, vp, vp, sz, i32, vp]
+    L.msm_sigs_chunk.argtypes = []
+    L.msm_sigs_chunk.restype = sz
+    L.msm_sigs_plan.argtypes = [i32, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz]
+    L.msm_sigs_reduce.argtypes = [i32, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

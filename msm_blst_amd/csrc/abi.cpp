@@ -27,6 +27,7 @@
 #include "points_mult.hpp"
 #include "pool.hpp"
 #include "ptr_walk.hpp"
+#include "sig_verify.hpp"
 #include "table_registry.hpp"
 #include "to_affine.hpp"
 
@@ -663,6 +664,125 @@ int pairing_checked(int dev, void *dst, uint8_t *is_one, size_t *nfail, const vo
   }
 }
 
+// ---- bulk signature verification (a loop over ref aggregate.c: core_verify, and the
+// pairing_chk_n_[mul_n_]aggr / commit / finalverify sequence per check) ----
+struct SigArgs {
+  int mode, scheme, dev;
+  uint8_t *status;
+  size_t *nfail;
+  const void *pks, *sigs, *msgs, *aug;
+  const size_t *pk_offsets, *msg_offsets, *offsets;
+  size_t msg_len, aug_len, k;
+  const byte *scalars;
+  size_t nbits, stride;
+  const byte *DST;
+  size_t DST_len;
+  int flags;
+  bool src_dev;
+  hipStream_t user;
+};
+
+int sigs_checked(const SigArgs &a) {
+  if (a.scheme != MSM_SIG_MIN_PK && a.scheme != MSM_SIG_MIN_SIG) return fail(MSM_E_ARG, "unknown scheme");
+  if (a.flags & ~(MSM_H2C_ENCODE | MSM_SIG_ENCODED)) return fail(MSM_E_ARG, "unknown flag bits");
+  const bool weighted = a.mode == SIG_BATCH && a.scalars && a.nbits;
+  if (a.mode == SIG_BATCH && a.scalars) {
+    if (a.nbits > 256) return fail(MSM_E_ARG, "nbits must be at most 256");
+    if (a.stride < (a.nbits + 7) / 8) return fail(MSM_E_ARG, "scalar_stride shorter than (nbits + 7) / 8");
+    if (a.stride > ((size_t)1 << 20)) return fail(MSM_E_ARG, "scalar_stride out of range");
+  }
+  const size_t k = a.k;
+  if (k == 0) return MSM_OK;  // nothing touched
+  if (!a.status && !a.nfail) return fail(MSM_E_ARG, "null status and nfail");
+  if (k > ((size_t)1 << 40)) return fail(MSM_E_ARG, "nchecks out of range");
+  if (a.mode != SIG_VERIFY) {
+    if (!a.offsets) return fail(MSM_E_ARG, "null offsets");
+    if (!seg_offsets_ok(a.offsets, k)) return fail(MSM_E_ARG, "offsets decrease");
+    if (a.offsets[k] > ((size_t)1 << 40)) return fail(MSM_E_ARG, "offsets out of range");
+  } else if (a.pk_offsets) {
+    if (!seg_offsets_ok(a.pk_offsets, k)) return fail(MSM_E_ARG, "pk_offsets decrease");
+    if (a.pk_offsets[k] > ((size_t)1 << 40)) return fail(MSM_E_ARG, "pk_offsets out of range");
+  }
+  const size_t r0 = sig_row_begin(a.mode, a.offsets, 0), r1 = sig_row_begin(a.mode, a.offsets, k);
+  const size_t k0 = sig_key_begin(a.mode, a.offsets, a.pk_offsets, 0), k1 = sig_key_begin(a.mode, a.offsets, a.pk_offsets, k);
+  const size_t s0 = sig_sig_begin(a.mode, a.offsets, 0), s1 = sig_sig_begin(a.mode, a.offsets, k);
+  if (k1 > k0 && !a.pks) return fail(MSM_E_ARG, "null public keys");
+  if (s1 > s0 && !a.sigs) return fail(MSM_E_ARG, "null signatures");
+  if (a.DST_len && !a.DST) return fail(MSM_E_ARG, "null DST");
+  if (a.aug_len > ((size_t)1 << 30)) return fail(MSM_E_ARG, "aug_len out of range");
+  if (a.msg_offsets) {
+    if (!seg_offsets_ok(a.msg_offsets, r1)) return fail(MSM_E_ARG, "message offsets decrease");
+    for (size_t i = r0; i < r1; ++i)
+      if (a.msg_offsets[i + 1] - a.msg_offsets[i] > ((size_t)1 << 30)) return fail(MSM_E_ARG, "a message longer than 2^30 bytes");
+    if (a.msg_offsets[r1] > a.msg_offsets[r0] && !a.msgs) return fail(MSM_E_ARG, "null msgs");
+  } else {
+    if (a.msg_len > ((size_t)1 << 30)) return fail(MSM_E_ARG, "msg_len out of range");
+    if (r1 > r0 && a.msg_len && !a.msgs) return fail(MSM_E_ARG, "null msgs");
+  }
+  const bool enc = (a.flags & MSM_SIG_ENCODED) != 0;
+  if (a.src_dev && (((uintptr_t)a.pks | (uintptr_t)a.sigs) & (enc ? 3 : 7)) != 0)
+    return fail(MSM_E_ARG, enc ? "device keys / signatures not 4-byte aligned" : "device keys / signatures not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (a.dev < 0 || a.dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  std::vector<uint8_t> own;  // nfail without status: counted from a buffer of our own
+  uint8_t *st = a.status;
+  try {
+    if (!st) {
+      own.resize(k);
+      st = own.data();
+    }
+    SigCall c;
+    c.mode = a.mode;
+    c.encoded = enc;
+    c.count = (a.flags & MSM_H2C_ENCODE) ? 1 : 2;
+    c.keys = a.pks, c.sigs = a.sigs;
+    c.scalars = weighted ? a.scalars : nullptr;
+    c.nbits = weighted ? (int)a.nbits : 0;
+    c.stride = a.stride;
+    c.m.msgs = (const uint8_t *)a.msgs;
+    c.m.offsets = a.msg_offsets;
+    c.m.msg_len = a.msg_len;
+    c.m.aug = a.aug_len ? (const uint8_t *)a.aug : nullptr;
+    c.m.aug_len = a.aug ? a.aug_len : 0;
+    H2cTemplate tmpl;
+    const int hg = a.scheme == MSM_SIG_MIN_PK ? 2 : 1;  // the group of the hashes
+    h2c_make_template(tmpl, a.DST, a.DST_len, (unsigned)(64 * c.count * hg));
+    c.tmpl = &tmpl;
+    c.o = a.offsets, c.pk = a.pk_offsets, c.k = k, c.src_dev = a.src_dev;
+    if (a.scheme == MSM_SIG_MIN_PK)
+      bulk_run<SigVerify<1>>(a.dev, a.scheme, a.src_dev, false, a.user, [&](SigVerify<1> &e, hipStream_t cs) { e.run(cs, c, st); });
+    else
+      bulk_run<SigVerify<2>>(a.dev, a.scheme, a.src_dev, false, a.user, [&](SigVerify<2> &e, hipStream_t cs) { e.run(cs, c, st); });
+    if (a.nfail) *a.nfail = k - (size_t)std::count(st, st + k, (uint8_t)0);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    if (a.status) memset(a.status, SIG_VERIFY_FAIL, k);
+    if (a.nfail) *a.nfail = k;
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
+int points_in_group_checked(int group, int dev, uint8_t *in_group, const void *points, size_t n, bool src_dev,
+                            hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (n == 0) return MSM_OK;  // nothing touched
+  if (!in_group || !points) return fail(MSM_E_ARG, "null in_group / points");
+  if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
+  if (src_dev && ((uintptr_t)points & 7) != 0) return fail(MSM_E_ARG, "device points not 8-byte aligned");
+  const int ndev = msm_device_count();
+  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    if (group == 1)
+      bulk_run<GroupScreen<1>>(dev, 1, src_dev, false, user, [&](GroupScreen<1> &e, hipStream_t cs) { e.run(cs, points, in_group, n, src_dev); });
+    else
+      bulk_run<GroupScreen<2>>(dev, 2, src_dev, false, user, [&](GroupScreen<2> &e, hipStream_t cs) { e.run(cs, points, in_group, n, src_dev); });
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    memset(in_group, 0, n);
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   size_t w = 0;
   while (n >>= 1) ++w;
@@ -1113,6 +1233,80 @@ int msm_fp12_final_exp(int device, void *dst_fp12, uint8_t *is_one, size_t *nfai
 }
 
 size_t msm_pairing_piece(size_t npairs) { return pair_piece_len(std::min(std::max(npairs, (size_t)1), pair_chunk())); }
+
+int msm_sigs_verify(int scheme, int device, uint8_t *status, size_t *nfail, const void *pks, const size_t *pk_offsets,
+                    const void *sigs, const void *msgs, const size_t *msg_offsets, size_t msg_len, const void *aug,
+                    size_t aug_len, size_t nchecks, const byte *DST, size_t DST_len, int flags, int src_on_device,
+                    void *hip_stream) {
+  return sigs_checked(SigArgs{SIG_VERIFY, scheme, device, status, nfail, pks, sigs, msgs, aug, pk_offsets, msg_offsets,
+                              nullptr, msg_len, aug_len, nchecks, nullptr, 0, 0, DST, DST_len, flags,
+                              src_on_device != 0, (hipStream_t)hip_stream});
+}
+
+int msm_sigs_aggregate_verify(int scheme, int device, uint8_t *status, size_t *nfail, const void *pks, const void *sigs,
+                              const void *msgs, const size_t *msg_offsets, size_t msg_len, const void *aug,
+                              size_t aug_len, const size_t *offsets, size_t nchecks, const byte *DST, size_t DST_len,
+                              int flags, int src_on_device, void *hip_stream) {
+  return sigs_checked(SigArgs{SIG_AGGREGATE, scheme, device, status, nfail, pks, sigs, msgs, aug, nullptr, msg_offsets,
+                              offsets, msg_len, aug_len, nchecks, nullptr, 0, 0, DST, DST_len, flags,
+                              src_on_device != 0, (hipStream_t)hip_stream});
+}
+
+int msm_sigs_batch_verify(int scheme, int device, uint8_t *status, size_t *nfail, const void *pks, const void *sigs,
+                          const byte *scalars, size_t nbits, size_t scalar_stride, const void *msgs,
+                          const size_t *msg_offsets, size_t msg_len, const void *aug, size_t aug_len,
+                          const size_t *offsets, size_t nchecks, const byte *DST, size_t DST_len, int flags,
+                          int src_on_device, void *hip_stream) {
+  return sigs_checked(SigArgs{SIG_BATCH, scheme, device, status, nfail, pks, sigs, msgs, aug, nullptr, msg_offsets,
+                              offsets, msg_len, aug_len, nchecks, scalars, nbits, scalar_stride, DST, DST_len, flags,
+                              src_on_device != 0, (hipStream_t)hip_stream});
+}
+
+int msm_points_in_group(int group, int device, uint8_t *in_group, const void *points_affine, size_t npoints,
+                        int src_on_device, void *hip_stream) {
+  return points_in_group_checked(group, device, in_group, points_affine, npoints, src_on_device != 0,
+                                 (hipStream_t)hip_stream);
+}
+
+size_t msm_sigs_chunk(void) { return sig_chunk(); }
+
+int msm_sigs_plan(int mode, const size_t *offsets, const size_t *pk_offsets, size_t nchecks, size_t c0, size_t chunk,
+                  size_t *c1, size_t counts[4], uint32_t *ent_check, uint32_t *ent_src, size_t *pair_off,
+                  size_t *key_off, size_t *sig_off, size_t capacity) {
+  if (mode < SIG_VERIFY || mode > SIG_BATCH || !c1 || !counts || chunk == 0 || c0 >= nchecks)
+    return fail(MSM_E_ARG, "bad mode / null c1 / counts / chunk 0 / c0 past the checks");
+  if (mode != SIG_VERIFY && (!offsets || !seg_offsets_ok(offsets, nchecks))) return fail(MSM_E_ARG, "null or decreasing offsets");
+  if (mode == SIG_VERIFY && pk_offsets && !seg_offsets_ok(pk_offsets, nchecks)) return fail(MSM_E_ARG, "pk_offsets decrease");
+  SigChunkPlan pl;
+  *c1 = sig_chunk_end(mode, offsets, pk_offsets, nchecks, c0, chunk);
+  sig_plan_chunk(pl, mode, offsets, pk_offsets, c0, *c1);
+  counts[0] = pl.nrows, counts[1] = pl.nkeys, counts[2] = pl.nsigs, counts[3] = pl.ent.size();
+  for (size_t i = 0; i < pl.ent.size() && i < capacity; ++i) {
+    if (ent_check) ent_check[i] = pl.ent[i].check;
+    if (ent_src) ent_src[i] = pl.ent[i].src;
+  }
+  for (size_t i = 0; i < pl.pair_off.size() && i < capacity; ++i)
+    if (pair_off) pair_off[i] = pl.pair_off[i];
+  for (size_t i = 0; i < pl.key_off.size() && i < capacity; ++i)
+    if (key_off) key_off[i] = pl.key_off[i];
+  for (size_t i = 0; i < pl.sig_off.size() && i < capacity; ++i)
+    if (sig_off) sig_off[i] = pl.sig_off[i];
+  return MSM_OK;
+}
+
+int msm_sigs_reduce(int mode, const size_t *offsets, const size_t *pk_offsets, size_t c0, size_t c1,
+                    const uint8_t *sig_codes, const uint8_t *key_codes, const uint8_t *late, const uint8_t *is_one,
+                    uint8_t *status) {
+  if (mode < SIG_VERIFY || mode > SIG_BATCH || c1 < c0 || !status || !is_one || (mode != SIG_VERIFY && !offsets))
+    return fail(MSM_E_ARG, "bad mode / range / null status / is_one / offsets");
+  SigChunkPlan pl;
+  sig_plan_chunk(pl, mode, offsets, pk_offsets, c0, c1);
+  std::vector<uint8_t> cc(c1 - c0);
+  sig_reduce(pl, mode, offsets, pk_offsets, sig_codes, key_codes, cc.data());
+  for (size_t j = 0; j < c1 - c0; ++j)
+    status[j] = sig_status(cc[j], late && late[j], is_one[j] == 1, pl.pair_off[j + 1] - pl.pair_off[j] - 1);
+  return MSM_OK;
+}
 
 const char *msm_last_error(void) { return g_err.c_str(); }
 

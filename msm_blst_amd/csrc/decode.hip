@@ -128,20 +128,6 @@ static __global__ void __launch_bounds__(128)
   if (comp == 0) status[t] = (uint8_t)st;
 }
 
-// r = [k] p for the constant k = hi 2^64 + lo of `bits` bits (top bit set), p
-// affine and not infinity; r enters as p
-template <class F>
-__device__ __forceinline__ void dec_times(Xyzz<F> &r, const Aff<F> &p, uint64_t hi, uint64_t lo, int bits) {
-  for (int b = bits - 2; b >= 0; --b) {
-    Xyzz<F> tmp = r;
-    xyzz_dbl(r, tmp);
-    if (((b >= 64 ? hi >> (b - 64) : lo >> b) & 1) != 0) xyzz_madd(r, p, false);  // uniform: k is a constant
-  }
-}
-constexpr unsigned __int128 DEC_ZZ = (unsigned __int128)DEC_Z_ABS * DEC_Z_ABS;  // z^2, 128 bits
-constexpr uint64_t DEC_ZZ_HI = (uint64_t)(DEC_ZZ >> 64), DEC_ZZ_LO = (uint64_t)DEC_ZZ;
-static_assert((DEC_ZZ_HI >> 63) == 1 && (DEC_Z_ABS >> 63) == 1, "top bits");
-
 // lane (pair) t < n: a status-0 point outside the prime-order subgroup gets
 // status 3 and the all-zero output; everything else stays as it is
 template <int G>
@@ -157,38 +143,7 @@ static __global__ void __launch_bounds__(128, 2) k_decode_group(uint64_t *out, u
   fp_from_blst(dec_c(p.y), o + 6 * G + 6 * comp);
   const bool zx = f_is_zero_exact(p.x), zy = f_is_zero_exact(p.y);
   const bool skip = status[t] != 0 || (zx && zy);
-  Xyzz<LF> q;
-  xyzz_from_aff(q, p, false);
-  LF ex, ey;  // [k]P must equal (ex, -ey), affine
-  if constexpr (G == 1) {
-    dec_times(q, p, DEC_ZZ_HI, DEC_ZZ_LO, 128);
-    ey = p.y;
-    dec_mulk(ex, p.x, DEC_BETA);
-  } else {
-    dec_times(q, p, 0, DEC_Z_ABS, 64);
-    // psi: conjugate, then the constants (cx = cx1 i)
-    const bool odd = pair_odd();
-    LF cx, cy, t1, t2;
-    fp_zero(cx.c);
-    Fp k;
-    fp_set(k, DEC_PSI_CX1);
-    dec_sel(cx.c, odd, k);
-    fp_set(cy.c, DEC_PSI_CY0);
-    fp_set(k, DEC_PSI_CY1);
-    dec_sel(cy.c, odd, k);
-    fp_cneg4(t1.c, p.x.c, odd);
-    fp_cneg4(t2.c, p.y.c, odd);
-    f_mul(ex, t1, cx);
-    f_mul(ey, t2, cy);
-  }
-  // q == (ex, -ey):  X == ex ZZ,  Y + ey ZZZ == 0
-  LF u, v;
-  f_mul_bs(u, ex, q.zz);
-  f_mul_bs(v, ey, q.zzz);
-  const bool eq_x = dec_eq(dec_c(q.x), dec_c(u)), eq_y = dec_sum_is_zero(dec_c(q.y), dec_c(v));
-  bool ok = eq_x & eq_y;
-  const bool q_inf = xyzz_is_inf(q);
-  ok = dec_all<G>(ok) && !q_inf;
+  const bool ok = dec_in_group<G>(p);  // (decode_dev.hpp)
   if (!skip && !ok) {
     Fp zero;
     fp_zero(zero);

@@ -35,6 +35,10 @@ class Decode {
   // with dst (host) and status written.
   void run(hipStream_t cs, const void *src, void *dst, uint8_t *status, size_t n, bool serialized, bool check_group,
            bool src_dev, bool dst_dev);
+  // one chunk, device to device, queued on s: the kernels alone, with the status
+  // bytes left in device memory at d_status (sig_verify.hip reads them there)
+  void kernels(hipStream_t s, const void *d_src, void *d_dst, uint8_t *d_status, size_t n, bool serialized,
+               bool check_group);
   size_t device_bytes() const { return in_.device_bytes() + out_.device_bytes() + dst_[0].bytes + dst_[1].bytes; }
   int device() const { return dev_; }
 
@@ -43,8 +47,6 @@ class Decode {
   DevBuf dst_[2];        // status bytes of a slot
   Stage in_, out_, st_;  // st_: the status bytes' pinned slots (they come down from dst_)
   ChunkPipe pipe_;       // (last: it waits for the queued work before the buffers go)
-  void kernels(hipStream_t s, const void *d_src, void *d_dst, uint8_t *d_status, size_t n, bool serialized,
-               bool check_group);
 };
 
 }  // namespace msm

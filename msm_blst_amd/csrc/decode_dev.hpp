@@ -1,8 +1,8 @@
 // decode_dev.hpp -- device helpers of the bulk point decoding that other kernels
-// share (decode.hip, hash_to_curve.hip): the constants of the square-root chain,
-// of the sign rule and of the endomorphisms, a^((p-3)/4) by fixed 2-bit windows,
-// square roots in Fp and, on lane pairs, in Fp2, and the sign of y.  Included by
-// .hip files only.
+// share (decode.hip, hash_to_curve.hip, sig_verify.hip): the constants of the
+// square-root chain, of the sign rule and of the endomorphisms, a^((p-3)/4) by
+// fixed 2-bit windows, square roots in Fp and, on lane pairs, in Fp2, the sign
+// of y, and the subgroup test.  Included by .hip files only.
 #pragma once
 #include "pair_kernels.hpp"
 
@@ -212,6 +212,63 @@ __device__ __forceinline__ bool dec_sign(const Fp2L &y) {
   const uint32_t par = pair_swap(own);
   const uint32_t im = pair_odd() ? own : par, re = pair_odd() ? par : own;
   return ((im & 2u) ? (re & 1u) : (im & 1u)) != 0;
+}
+
+// r = [k] p for the constant k = hi 2^64 + lo of `bits` bits (top bit set), p
+// affine and not infinity; r enters as p
+template <class F>
+__device__ __forceinline__ void dec_times(Xyzz<F> &r, const Aff<F> &p, uint64_t hi, uint64_t lo, int bits) {
+  for (int b = bits - 2; b >= 0; --b) {
+    Xyzz<F> tmp = r;
+    xyzz_dbl(r, tmp);
+    if (((b >= 64 ? hi >> (b - 64) : lo >> b) & 1) != 0) xyzz_madd(r, p, false);  // uniform: k is a constant
+  }
+}
+constexpr unsigned __int128 DEC_ZZ = (unsigned __int128)DEC_Z_ABS * DEC_Z_ABS;  // z^2, 128 bits
+constexpr uint64_t DEC_ZZ_HI = (uint64_t)(DEC_ZZ >> 64), DEC_ZZ_LO = (uint64_t)DEC_ZZ;
+static_assert((DEC_ZZ_HI >> 63) == 1 && (DEC_Z_ABS >> 63) == 1, "top bits");
+
+// The reference's endomorphism tests (Scott, eprint 2021/1130) on an affine point
+// of the curve that is not infinity: G1 [z^2]P == -sigma^2(P), G2 [|z|]P ==
+// -psi(P), on ec.hpp's xyzz formulas.  G2: both lanes of the pair get the
+// verdict.  (k_decode_group of decode.hip and k_sig_screen of sig_verify.hip;
+// the all-zero point runs through the same instructions and its verdict is
+// not used.)
+template <int G>
+__device__ __forceinline__ bool dec_in_group(const Aff<typename DecLane<G>::LF> &p) {
+  typedef typename DecLane<G>::LF LF;
+  Xyzz<LF> q;
+  xyzz_from_aff(q, p, false);
+  LF ex, ey;  // [k]P must equal (ex, -ey), affine
+  if constexpr (G == 1) {
+    dec_times(q, p, DEC_ZZ_HI, DEC_ZZ_LO, 128);
+    ey = p.y;
+    dec_mulk(ex, p.x, DEC_BETA);
+  } else {
+    dec_times(q, p, 0, DEC_Z_ABS, 64);
+    // psi: conjugate, then the constants (cx = cx1 i)
+    const bool odd = pair_odd();
+    LF cx, cy, t1, t2;
+    fp_zero(cx.c);
+    Fp k;
+    fp_set(k, DEC_PSI_CX1);
+    dec_sel(cx.c, odd, k);
+    fp_set(cy.c, DEC_PSI_CY0);
+    fp_set(k, DEC_PSI_CY1);
+    dec_sel(cy.c, odd, k);
+    fp_cneg4(t1.c, p.x.c, odd);
+    fp_cneg4(t2.c, p.y.c, odd);
+    f_mul(ex, t1, cx);
+    f_mul(ey, t2, cy);
+  }
+  // q == (ex, -ey):  X == ex ZZ,  Y + ey ZZZ == 0
+  LF u, v;
+  f_mul_bs(u, ex, q.zz);
+  f_mul_bs(v, ey, q.zzz);
+  const bool eq_x = dec_eq(dec_c(q.x), dec_c(u)), eq_y = dec_sum_is_zero(dec_c(q.y), dec_c(v));
+  bool ok = eq_x & eq_y;
+  const bool q_inf = xyzz_is_inf(q);
+  return dec_all<G>(ok) && !q_inf;
 }
 
 }  // namespace msm
