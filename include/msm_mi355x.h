@@ -197,6 +197,12 @@ int msm_device_count(void);
  * in the same run): out = {v_mad_u64_u32 lane-ops/s, Fp-mul/s, G1 xyzz madd/s
  * (the accumulation's loop body, rows in cache), device ms spent} */
 int msm_valu_probe(int device, double out[4]);
+/* Device self-test of the two Montgomery column forms (extension): every lane t of
+ * `lanes` reads 8 field elements a0..a7 (internal form: 14 words of 28 bits, each
+ * normalized and < 2p) and writes 11: a0 a1, a0^2, a0 a1 + a2 a3, the xyzz point
+ * (a0..a3) plus the affine row (a4, a5) (negated on odd lanes), and the xyzz point
+ * (a0..a3) plus the xyzz point (a4..a7).  form 0: split columns, 1: single chain. */
+int msm_fp_form_ops(int device, int form, const uint32_t *in, size_t lanes, uint32_t *out);
 /* Engines behind the blst-named entry points (no caller context: ref
  * multi_scalar.c:581-607) live in a process-wide pool per (device, kind,
  * window): a call leases one, a concurrent call creates another, and a returned

@@ -1369,6 +1369,17 @@ int msm_valu_probe(int device, double out[4]) {
   }
 }
 
+int msm_fp_form_ops(int device, int form, const uint32_t *in, size_t lanes, uint32_t *out) {
+  if (!in || !out || !lanes || (form != 0 && form != 1)) return fail(MSM_E_ARG, "bad in / out / lanes / form");
+  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
+  try {
+    form_ops(device, form, in, lanes, out);
+    return MSM_OK;
+  } catch (const std::exception &e) {
+    return fail(MSM_E_HIP, e.what());
+  }
+}
+
 int msm_ctx_create(msm_ctx **ctx, int group, int device, int window_bits) {
   if (!ctx || (group != 1 && group != 2)) return fail(MSM_E_ARG, "bad ctx/group");
   if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");

@@ -525,6 +525,22 @@ static __global__ void __launch_bounds__(256)
 #ifndef MSM_SEGSUM_PREFETCH
 #define MSM_SEGSUM_PREFETCH 0
 #endif
+// MSM_SEGSUM_CHAIN (build-time A/B knob): 1 builds the G1 segment sums' general
+// add (level 0 of the reduction and the levels after it) with the single-chain
+// Montgomery columns (fp.hpp MulChain); same values
+#ifndef MSM_SEGSUM_CHAIN
+#define MSM_SEGSUM_CHAIN 0
+#endif
+template <int G>
+struct SegsumForm {
+  typedef MulSplit T;
+};
+#if MSM_SEGSUM_CHAIN
+template <>
+struct SegsumForm<1> {
+  typedef MulChain T;
+};
+#endif
 // dst[t] = sum_{k in [starts[t], starts[t+1])} src[idx ? idx[k] : k]   (xyzz)
 // for each of gridDim.y MSMs of a batch group: MSM blockIdx.y reads src +
 // y src_stride and writes dst + y dst_stride (the same plan for every MSM)
@@ -547,12 +563,12 @@ __device__ __forceinline__ void segsum_one(const Xyzz<typename FieldOf<G>::F> *_
     for (uint32_t k = lo + 1; k < hi; ++k) {
       Xyzz<F> a = nxt;
       if (k + 1 < hi) nxt = ld16(&src[idx ? idx[k + 1] : k + 1]);
-      xyzz_add(acc, a);
+      xyzz_add<F, AddRegrouped<F>::value, typename SegsumForm<G>::T>(acc, a);
     }
 #else
     for (uint32_t k = lo + 1; k < hi; ++k) {
       Xyzz<F> a = ld16(&src[idx ? idx[k] : k]);
-      xyzz_add(acc, a);
+      xyzz_add<F, AddRegrouped<F>::value, typename SegsumForm<G>::T>(acc, a);
     }
 #endif
   }

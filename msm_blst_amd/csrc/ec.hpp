@@ -57,7 +57,7 @@ MSM_FN void xyzz_from_aff(Xyzz<F> &r, const Aff<F> &p, bool neg) {
 // doubling of an xyzz point given in S (dbl-2008-s-1):
 //   U = 2Y, V = U^2, W = U V, S = X V, M = 3 X^2 (+ a ZZ^2, a = 0)
 //   X3 = M^2 - 2S, Y3 = M (S - X3) - W Y, ZZ3 = V ZZ, ZZZ3 = W ZZZ
-template <class F>
+template <class F, class CF = MulSplit>
 MSM_FN void xyzz_dbl(Xyzz<F> &r, const Xyzz<F> &a) {
   if (xyzz_is_inf(a)) {
     r = a;
@@ -72,20 +72,20 @@ MSM_FN void xyzz_dbl(Xyzz<F> &r, const Xyzz<F> &a) {
   // (DESIGN 11).
   F U, V, W, S, M, t, X3;
   f_add(U, a.y, a.y);      // < 4p lazy
-  f_sqr(V, U);             // S
-  f_mul(W, V, U);          // S
-  f_mul(S, a.x, V);        // S
-  f_mul(r.zz, V, a.zz);    // ZZ3 = V ZZ (V, ZZ die)
-  f_mul(r.zzz, W, a.zzz);  // ZZZ3 = W ZZZ
-  f_sqr(M, a.x);           // S (X dies)
+  f_sqr(V, U, CF{});             // S
+  f_mul(W, V, U, CF{});          // S
+  f_mul(S, a.x, V, CF{});        // S
+  f_mul(r.zz, V, a.zz, CF{});    // ZZ3 = V ZZ (V, ZZ die)
+  f_mul(r.zzz, W, a.zzz, CF{});  // ZZZ3 = W ZZZ
+  f_sqr(M, a.x, CF{});           // S (X dies)
   f_mul3(M, M);            // < 6p lazy
-  f_sqr(X3, M);            // S
+  f_sqr(X3, M, CF{});            // S
   F z;
   f_zero(z);
   f_sub_2x(X3, X3, z, S);  // M^2 + 8p - 2S   < 10p
   f_norm(X3);              // X
   f_sub16(t, S, X3);       // < 18p
-  f_mul_sub(r.y, t, M, W, a.y);  // Y3 = M (S - X3) - W Y   S (one reduction)
+  f_mul_sub(r.y, t, M, W, a.y, CF{});  // Y3 = M (S - X3) - W Y   S (one reduction)
   r.x = X3;
 }
 
@@ -102,7 +102,7 @@ MSM_FN void xyzz_dbl(Xyzz<F> &r, const Xyzz<F> &a) {
 // at 8p, past the < 6p f_sqr and f_mul_sub are proven for
 // (tests/test_first_pair_bounds.py).  X2 and +-Y2 are in class S like the
 // products they replace, so every later range is the generic path's.
-template <class F>
+template <class F, class CF = MulSplit>
 MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg, bool acc_affine = false) {
   if (xyzz_is_inf(acc)) {
     xyzz_from_aff(acc, p, neg);
@@ -119,22 +119,22 @@ MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg, bool acc_affine =
     if (neg) f_nred(y2);        // S2 = +-Y2            S
     R = y2;
   } else {
-    f_mul_bs(P, p.x, acc.zz);   // U2 = X2 ZZ1          S
-    f_mul_bs(R, y2, acc.zzz);   // S2 = Y2 ZZZ1         S
+    f_mul_bs(P, p.x, acc.zz, CF{});   // U2 = X2 ZZ1          S
+    f_mul_bs(R, y2, acc.zzz, CF{});   // S2 = Y2 ZZZ1         S
   }
   f_sub16(P, P, acc.x);    // P = U2 - X1          < 18p lazy
   f_sub4(R, R, acc.y);     // R = S2 - Y1          < 6p lazy
-  f_sqr(PP, P);            // PP                   S
+  f_sqr(PP, P, CF{});            // PP                   S
   if (__builtin_expect(f_is_zero_S(PP), 0)) {
     // X1 == X2: either P == bucket (double it) or P == -bucket (infinity)
     F RR;
-    f_sqr(RR, R);
+    f_sqr(RR, R, CF{});
     if (f_is_zero_S(RR)) {
       // +-P equals the bucket: double the bucket itself (still untouched
       // here), so the affine operand dies after U2 and S2 instead of staying
       // live through the whole madd for this branch
       Xyzz<F> b = acc;
-      xyzz_dbl(acc, b);
+      xyzz_dbl<F, CF>(acc, b);
     } else {
       xyzz_set_inf(acc);
     }
@@ -149,64 +149,64 @@ MSM_FN void xyzz_madd(Xyzz<F> &acc, const Aff<F> &p, bool neg, bool acc_affine =
   if (acc_affine) {
     acc.zz = PP;                     // ZZ3 = PP             S
   } else {
-    f_mul_bs(acc.zz, acc.zz, PP);    // ZZ3 = ZZ1 PP         S
+    f_mul_bs(acc.zz, acc.zz, PP, CF{});    // ZZ3 = ZZ1 PP         S
   }
-  f_mul_bs(PPP, P, PP);         // S
-  f_mul_bs(acc.x, acc.x, PP);      // Q = X1 PP  (in place of X1)   S
+  f_mul_bs(PPP, P, PP, CF{});         // S
+  f_mul_bs(acc.x, acc.x, PP, CF{});      // Q = X1 PP  (in place of X1)   S
   if (acc_affine) {
     acc.zzz = PPP;                   // ZZZ3 = PPP           S
   } else {
-    f_mul_bs(acc.zzz, acc.zzz, PPP); // ZZZ3 = ZZZ1 PPP      S
+    f_mul_bs(acc.zzz, acc.zzz, PPP, CF{}); // ZZZ3 = ZZZ1 PPP      S
   }
   F X3;
-  f_sqr(X3, R);            // R^2                  S
+  f_sqr(X3, R, CF{});            // R^2                  S
   f_sub_2x(X3, X3, PPP, acc.x);  // R^2 + 8p - PPP - 2Q   < 10p
   f_norm(X3);              // X3 = R^2 - PPP - 2Q  X
   f_sub16(t, acc.x, X3);   // Q - X3  < 18p
-  f_mul_sub(acc.y, t, R, acc.y, PPP);  // Y3 = R (Q - X3) - Y1 PPP   S (one reduction)
+  f_mul_sub(acc.y, t, R, acc.y, PPP, CF{});  // Y3 = R (Q - X3) - Y1 PPP   S (one reduction)
   acc.x = X3;
 }
 
 // acc += b, both xyzz in S: the 13-reduction form (U1 = X1 ZZ2 and S1 = Y1 ZZZ2
 // reduced on their own).  Kept for the one-lane Fp2 and for hash_to_curve.hip,
 // see xyzz_add.
-template <class F>
+template <class F, class CF = MulSplit>
 MSM_FN void xyzz_add_u1s1(Xyzz<F> &acc, const Xyzz<F> &b) {
   // Computed in place so that b dies early and at most ~8 field elements are
   // live (G2: 28 VGPRs each): acc is first rewritten as the representative
   // (U1, S1, ZZZ1 ZZZ2, ZZ1 ZZ2) of the same point, which is also what the
   // doubling branch doubles.
   F P, R, PP, PPP, t;
-  f_mul_bs(acc.x, acc.x, b.zz);    // U1 = X1 ZZ2          S
-  f_mul_bs(acc.y, acc.y, b.zzz);   // S1 = Y1 ZZZ2         S
-  f_mul_bs(P, b.x, acc.zz);        // U2 = X2 ZZ1          S
+  f_mul_bs(acc.x, acc.x, b.zz, CF{});    // U1 = X1 ZZ2          S
+  f_mul_bs(acc.y, acc.y, b.zzz, CF{});   // S1 = Y1 ZZZ2         S
+  f_mul_bs(P, b.x, acc.zz, CF{});        // U2 = X2 ZZ1          S
   f_sub4(P, P, acc.x);          // P = U2 - U1          < 6p
-  f_mul_bs(R, b.y, acc.zzz);       // S2 = Y2 ZZZ1         S
+  f_mul_bs(R, b.y, acc.zzz, CF{});       // S2 = Y2 ZZZ1         S
   f_sub4(R, R, acc.y);          // R = S2 - S1          < 6p
-  f_mul_bs(acc.zz, acc.zz, b.zz);
-  f_mul_bs(acc.zzz, acc.zzz, b.zzz);
-  f_sqr(PP, P);
+  f_mul_bs(acc.zz, acc.zz, b.zz, CF{});
+  f_mul_bs(acc.zzz, acc.zzz, b.zzz, CF{});
+  f_sqr(PP, P, CF{});
   if (__builtin_expect(f_is_zero_S(PP), 0)) {
     F RR;
-    f_sqr(RR, R);
+    f_sqr(RR, R, CF{});
     if (f_is_zero_S(RR)) {
       Xyzz<F> a = acc;
-      xyzz_dbl(acc, a);
+      xyzz_dbl<F, CF>(acc, a);
     } else {
       xyzz_set_inf(acc);
     }
     return;
   }
-  f_mul_bs(acc.zz, acc.zz, PP);    // ZZ3 = ZZ1 ZZ2 PP
-  f_mul_bs(PPP, P, PP);
-  f_mul_bs(acc.x, acc.x, PP);      // Q = U1 PP  (in place of U1)
-  f_mul_bs(acc.zzz, acc.zzz, PPP); // ZZZ3 = ZZZ1 ZZZ2 PPP
+  f_mul_bs(acc.zz, acc.zz, PP, CF{});    // ZZ3 = ZZ1 ZZ2 PP
+  f_mul_bs(PPP, P, PP, CF{});
+  f_mul_bs(acc.x, acc.x, PP, CF{});      // Q = U1 PP  (in place of U1)
+  f_mul_bs(acc.zzz, acc.zzz, PPP, CF{}); // ZZZ3 = ZZZ1 ZZZ2 PPP
   F X3;
-  f_sqr(X3, R);
+  f_sqr(X3, R, CF{});
   f_sub_2x(X3, X3, PPP, acc.x);
   f_norm(X3);                   // X3 = R^2 - PPP - 2Q  X
   f_sub16(t, acc.x, X3);
-  f_mul_sub(acc.y, t, R, acc.y, PPP);  // Y3 = R (Q - X3) - S1 PPP   S (one reduction)
+  f_mul_sub(acc.y, t, R, acc.y, PPP, CF{});  // Y3 = R (Q - X3) - S1 PPP   S (one reduction)
   acc.x = X3;
 }
 
@@ -227,7 +227,7 @@ struct AddRegrouped<Fp2> {
 };
 
 // the regrouped add of two finite points
-template <class F>
+template <class F, class CF = MulSplit>
 MSM_FN void xyzz_add_regrouped(Xyzz<F> &acc, const Xyzz<F> &b) {
   // 12 products and 2 squares with 11 Montgomery reductions instead of 13
   // (DESIGN 23): U1 = X1 ZZ2 and S1 = Y1 ZZZ2 are never reduced on their own.
@@ -240,33 +240,33 @@ MSM_FN void xyzz_add_regrouped(Xyzz<F> &acc, const Xyzz<F> &b) {
   // (4p - d) < 10p 2p + 10p 4p = 60 p^2 and every column stays below 2^64
   // (tests/test_xyzz_add_bounds.py).
   F P, R, PP, PPP, V, W, t;
-  f_mul_sub_bs(P, b.x, acc.zz, acc.x, b.zz);    // P = X2 ZZ1 - X1 ZZ2     S
-  f_mul_sub_bs(R, b.y, acc.zzz, acc.y, b.zzz);  // R = Y2 ZZZ1 - Y1 ZZZ2   S
-  f_sqr(PP, P);                              // PP                      S
+  f_mul_sub_bs(P, b.x, acc.zz, acc.x, b.zz, CF{});    // P = X2 ZZ1 - X1 ZZ2     S
+  f_mul_sub_bs(R, b.y, acc.zzz, acc.y, b.zzz, CF{});  // R = Y2 ZZZ1 - Y1 ZZZ2   S
+  f_sqr(PP, P, CF{});                              // PP                      S
   if (__builtin_expect(f_is_zero_S(PP), 0)) {
     F RR;
-    f_sqr(RR, R);
+    f_sqr(RR, R, CF{});
     if (f_is_zero_S(RR)) {
       // b equals acc: double acc itself, which is still the untouched input
       Xyzz<F> a = acc;
-      xyzz_dbl(acc, a);
+      xyzz_dbl<F, CF>(acc, a);
     } else {
       xyzz_set_inf(acc);
     }
     return;
   }
-  f_mul_bs(V, b.zz, PP);           // V = ZZ2 PP           S  (ZZ2 dies)
-  f_mul_bs(acc.zz, acc.zz, V);     // ZZ3 = ZZ1 V          S
-  f_mul_bs(acc.x, acc.x, V);       // Q = X1 V  (in place of X1)   S  (V dies)
-  f_mul_bs(PPP, P, PP);            // PPP                  S  (P, PP die)
-  f_mul_bs(W, b.zzz, PPP);         // W = ZZZ2 PPP         S  (ZZZ2 dies)
-  f_mul_bs(acc.zzz, acc.zzz, W);   // ZZZ3 = ZZZ1 W        S
+  f_mul_bs(V, b.zz, PP, CF{});           // V = ZZ2 PP           S  (ZZ2 dies)
+  f_mul_bs(acc.zz, acc.zz, V, CF{});     // ZZ3 = ZZ1 V          S
+  f_mul_bs(acc.x, acc.x, V, CF{});       // Q = X1 V  (in place of X1)   S  (V dies)
+  f_mul_bs(PPP, P, PP, CF{});            // PPP                  S  (P, PP die)
+  f_mul_bs(W, b.zzz, PPP, CF{});         // W = ZZZ2 PPP         S  (ZZZ2 dies)
+  f_mul_bs(acc.zzz, acc.zzz, W, CF{});   // ZZZ3 = ZZZ1 W        S
   F X3;
-  f_sqr(X3, R);
+  f_sqr(X3, R, CF{});
   f_sub_2x(X3, X3, PPP, acc.x);
   f_norm(X3);                   // X3 = R^2 - PPP - 2Q  X
   f_sub16(t, acc.x, X3);
-  f_mul_sub_bs(acc.y, t, R, acc.y, W);  // Y3 = R (Q - X3) - Y1 W   S (one reduction; R is S here)
+  f_mul_sub_bs(acc.y, t, R, acc.y, W, CF{});  // Y3 = R (Q - X3) - Y1 W   S (one reduction; R is S here)
   acc.x = X3;
 }
 
@@ -274,15 +274,15 @@ MSM_FN void xyzz_add_regrouped(Xyzz<F> &acc, const Xyzz<F> &b) {
 // (xyzz_add<F, false>(acc, b)): the cofactor-clearing kernel of
 // hash_to_curve.hip, two ladders and five adds in one body, lost a wave (G1) and
 // spilled (G2) with the regrouped one.
-template <class F, bool REGROUP = AddRegrouped<F>::value>
+template <class F, bool REGROUP = AddRegrouped<F>::value, class CF = MulSplit>
 MSM_FN void xyzz_add(Xyzz<F> &acc, const Xyzz<F> &b) {
   if (xyzz_is_inf(b)) return;
   if (xyzz_is_inf(acc)) {
     acc = b;
     return;
   }
-  if constexpr (REGROUP) xyzz_add_regrouped(acc, b);
-  else xyzz_add_u1s1(acc, b);
+  if constexpr (REGROUP) xyzz_add_regrouped<F, CF>(acc, b);
+  else xyzz_add_u1s1<F, CF>(acc, b);
 }
 
 }  // namespace msm

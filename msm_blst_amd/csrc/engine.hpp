@@ -636,6 +636,9 @@ void weighted_bucket_sum(void *ret_jac, const void *buckets_blst, size_t nb, con
 // VALU ceilings of this device, measured now (probe.hip): {mad lane-ops/s,
 // Fp-mul/s, G1 madd/s, device ms spent}
 void valu_probe(int device, double out[4]);
+// one of each Montgomery product and G1 point formula per lane in the split (form 0)
+// or single-chain (form 1) column form (probe.hip k_form_ops)
+void form_ops(int device, int form, const uint32_t *in, size_t lanes, uint32_t *out);
 // device self-tests (engine.hip)
 template <int G>
 void test_field(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);

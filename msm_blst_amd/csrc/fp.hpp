@@ -243,6 +243,208 @@ MSM_FN void fp_sqr(Fp &r, const Fp &a) {
   r.v[NL - 1] = top32(acc);
 }
 
+// ------------------------------------------------ single-chain columns ---
+// The products above leave the order of a column's sum to the compiler, which
+// starts the a b and early m p products on a second chain from 0 and merges
+// that chain with the previous column's carry (one v_lshl_add_u64 x, 0, carry
+// per column: 26 per product).  A v_mad_u64_u32 chain takes one 64-bit addend
+// for free, so the forms below seed each column's chain with the carry
+// instead: the same sum in another order, every product bit-identical.
+// The order is fixed from source by pinning, after each column's carry, first
+// the carry and then every register value the next column multiplies (the
+// first operands' limbs and the earlier m[i]): the products then rank above
+// the carry and the carry is added first.  A pin is an empty asm statement
+// (no instruction; nothing in the host build), one per column, more only
+// where a statement's operand limit (15 tied operands) forces it.
+// Selected per caller by tag (f_mul(r, a, b, MulChain{}), xyzz_madd<F,
+// MulChain>, ...); MulSplit, every function's default, is the forms above.
+// Which kernels ask for MulChain, and what it measured: DESIGN 25.
+struct MulSplit {};
+struct MulChain {};
+
+#ifndef MSM_FP_HOST_TEST
+#define MSM_PIN1(o) "+v"(p[o])
+#define MSM_PIN2(o) MSM_PIN1(o), MSM_PIN1(o + 1)
+#define MSM_PIN4(o) MSM_PIN2(o), MSM_PIN2(o + 2)
+#define MSM_PIN8(o) MSM_PIN4(o), MSM_PIN4(o + 4)
+#define MSM_PIN_CASE(n, ...)                               \
+  if constexpr (N == n) {                                  \
+    if constexpr (C) asm volatile("" : "+v"(*c), __VA_ARGS__); \
+    else asm volatile("" : __VA_ARGS__);                   \
+  }
+// one statement: the carry (C) and N <= 14 limbs, or N <= 15 limbs
+template <bool C, int N>
+MSM_FN void pin_stmt(uint64_t *c, uint32_t *p) {
+  static_assert(N >= 0 && N + (C ? 1 : 0) <= 15, "asm operand limit");
+  if constexpr (N == 0 && C) asm volatile("" : "+v"(*c));
+  MSM_PIN_CASE(1, MSM_PIN1(0))
+  MSM_PIN_CASE(2, MSM_PIN2(0))
+  MSM_PIN_CASE(3, MSM_PIN2(0), MSM_PIN1(2))
+  MSM_PIN_CASE(4, MSM_PIN4(0))
+  MSM_PIN_CASE(5, MSM_PIN4(0), MSM_PIN1(4))
+  MSM_PIN_CASE(6, MSM_PIN4(0), MSM_PIN2(4))
+  MSM_PIN_CASE(7, MSM_PIN4(0), MSM_PIN2(4), MSM_PIN1(6))
+  MSM_PIN_CASE(8, MSM_PIN8(0))
+  MSM_PIN_CASE(9, MSM_PIN8(0), MSM_PIN1(8))
+  MSM_PIN_CASE(10, MSM_PIN8(0), MSM_PIN2(8))
+  MSM_PIN_CASE(11, MSM_PIN8(0), MSM_PIN2(8), MSM_PIN1(10))
+  MSM_PIN_CASE(12, MSM_PIN8(0), MSM_PIN4(8))
+  MSM_PIN_CASE(13, MSM_PIN8(0), MSM_PIN4(8), MSM_PIN1(12))
+  MSM_PIN_CASE(14, MSM_PIN8(0), MSM_PIN4(8), MSM_PIN2(12))
+  MSM_PIN_CASE(15, MSM_PIN8(0), MSM_PIN4(8), MSM_PIN2(12), MSM_PIN1(14))
+}
+#undef MSM_PIN_CASE
+#undef MSM_PIN8
+#undef MSM_PIN4
+#undef MSM_PIN2
+#undef MSM_PIN1
+template <int N>
+MSM_FN void pin_more(uint32_t *p) {
+  if constexpr (N > 15) {
+    pin_stmt<false, 15>(nullptr, p);
+    pin_more<N - 15>(p + 15);
+  } else if constexpr (N > 0) {
+    pin_stmt<false, N>(nullptr, p);
+  }
+}
+#endif
+// the carry, then the N values at p, in that order
+template <int N>
+MSM_FN void pin_col(uint64_t &c, uint32_t *p) {
+#ifndef MSM_FP_HOST_TEST
+  if constexpr (N > 14) {
+    pin_stmt<true, 14>(&c, p);
+    pin_more<N - 14>(p + 14);
+  } else {
+    pin_stmt<true, N>(&c, p);
+  }
+#else
+  (void)c;
+  (void)p;
+#endif
+}
+
+// Column K of (sum_j A[j] B[j]) / R mod p and, by recursion, every later one.
+// Column K multiplies A[j][i] B[j][K - i] and m[i] p[K - i] for i in [LO, HI]
+// (m: i < K in the low half); the A limbs and m[i] of exactly that range are
+// pinned, so no operand is kept live past its last column.  A pinned limb is a
+// new value to the compiler: an A[j] that the caller still needs afterwards
+// costs 14 moves, one that dies in the product costs nothing, so callers put
+// the operand that dies first (in xyzz_madd and xyzz_add that is a[j] as
+// written, but for the subtrahend pair of f_mul_sub).
+template <int NP, int K>
+MSM_FN void chain_cols(Fp &r, uint64_t acc, uint32_t (&m)[NL], uint32_t (&A)[NP][NL], const uint32_t (&B)[NP][NL]) {
+  constexpr int LO = K < NL ? 0 : K - NL + 1, HI = K < NL ? K : NL - 1;
+  constexpr int NB = HI - LO + 1, NM = K < NL ? K : NB;
+  if constexpr (K > 0) {
+    uint32_t t[NP * NB + NM];
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+#pragma unroll
+      for (int i = 0; i < NB; ++i) t[j * NB + i] = A[j][LO + i];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) t[NP * NB + i] = m[LO + i];
+    pin_col<NP * NB + NM>(acc, t);
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+#pragma unroll
+      for (int i = 0; i < NB; ++i) A[j][LO + i] = t[j * NB + i];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) m[LO + i] = t[NP * NB + i];
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+#pragma unroll
+    for (int i = LO; i <= HI; ++i) acc = mad64(A[j][i], B[j][K - i], acc);
+#pragma unroll
+  for (int i = LO; i < LO + NM; ++i) acc = mad64(m[i], P28[K - i], acc);
+  if constexpr (K < NL) {
+    m[K] = ((uint32_t)acc * N0P) & MASK;
+    acc = mad64(m[K], P28[0], acc);
+  } else {
+    r.v[K - NL] = (uint32_t)acc & MASK;
+  }
+  acc >>= 28;
+  if constexpr (K < 2 * NL - 2) chain_cols<NP, K + 1>(r, acc, m, A, B);
+  else r.v[NL - 1] = top32(acc);
+}
+template <int NP>
+MSM_FN void fp_mulsum_chain(Fp &r, const Fp *const (&a)[NP], const Fp *const (&b)[NP]) {
+  uint32_t A[NP][NL], B[NP][NL], m[NL];
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      A[j][i] = a[j]->v[i];
+      B[j][i] = b[j]->v[i];
+    }
+  chain_cols<NP, 0>(r, 0, m, A, B);
+}
+// Same contracts (ranges, aliasing) and same values as fp_mul, fp_mul2, fp_mul4.
+MSM_FN void fp_mul(Fp &r, const Fp &a, const Fp &b, MulChain) {
+  const Fp *const x[1] = {&a}, *const y[1] = {&b};
+  fp_mulsum_chain<1>(r, x, y);
+}
+MSM_FN void fp_mul2(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d, MulChain) {
+  const Fp *const x[2] = {&a, &c}, *const y[2] = {&b, &d};
+  fp_mulsum_chain<2>(r, x, y);
+}
+MSM_FN void fp_mul4(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d, const Fp &e, const Fp &f, const Fp &g,
+                    const Fp &h, MulChain) {
+  const Fp *const x[4] = {&a, &c, &e, &g}, *const y[4] = {&b, &d, &f, &h};
+  fp_mulsum_chain<4>(r, x, y);
+}
+// fp_sqr with the carry seeding the column: the cross sum x keeps its own chain
+// from 0 and add_dbl(x, carry) starts the rest (the square term and the m p).
+template <int K>
+MSM_FN void chain_sqr_cols(Fp &r, uint64_t acc, uint32_t (&m)[NL], uint32_t (&A)[NL]) {
+  constexpr int LO = K < NL ? 0 : K - NL + 1, HI = K < NL ? K : NL - 1;
+  constexpr int NB = HI - LO + 1, NM = K < NL ? K : NB;
+  if constexpr (K > 0) {
+    // the cross sum starts from 0 and needs no pin; the square term does
+    constexpr int SQ = (K & 1) == 0 ? 1 : 0;
+    uint32_t t[SQ + NM];
+    if constexpr (SQ) t[0] = A[K / 2];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) t[SQ + i] = m[LO + i];
+    pin_col<SQ + NM>(acc, t);
+    if constexpr (SQ) A[K / 2] = t[0];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) m[LO + i] = t[SQ + i];
+  }
+  if constexpr (NB > 1) {
+    uint64_t x = 0;
+#pragma unroll
+    for (int i = LO; 2 * i < K; ++i) x = mad64(A[i], A[K - i], x);
+    acc = add_dbl(x, acc);
+  }
+  if constexpr ((K & 1) == 0) acc = mad64(A[K / 2], A[K / 2], acc);
+#pragma unroll
+  for (int i = LO; i < LO + NM; ++i) acc = mad64(m[i], P28[K - i], acc);
+  if constexpr (K < NL) {
+    m[K] = ((uint32_t)acc * N0P) & MASK;
+    acc = mad64(m[K], P28[0], acc);
+  } else {
+    r.v[K - NL] = (uint32_t)acc & MASK;
+  }
+  acc >>= 28;
+  if constexpr (K < 2 * NL - 2) chain_sqr_cols<K + 1>(r, acc, m, A);
+  else r.v[NL - 1] = top32(acc);
+}
+MSM_FN void fp_sqr(Fp &r, const Fp &a, MulChain) {
+  uint32_t A[NL], m[NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) A[i] = a.v[i];
+  chain_sqr_cols<0>(r, 0, m, A);
+}
+MSM_FN void fp_mul(Fp &r, const Fp &a, const Fp &b, MulSplit) { fp_mul(r, a, b); }
+MSM_FN void fp_mul2(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d, MulSplit) { fp_mul2(r, a, b, c, d); }
+MSM_FN void fp_mul4(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d, const Fp &e, const Fp &f, const Fp &g,
+                    const Fp &h, MulSplit) {
+  fp_mul4(r, a, b, c, d, e, f, g, h);
+}
+MSM_FN void fp_sqr(Fp &r, const Fp &a, MulSplit) { fp_sqr(r, a); }
+
 // lazy add: no carry propagation
 MSM_FN void fp_add(Fp &r, const Fp &a, const Fp &b) {
 #pragma unroll
@@ -528,6 +730,33 @@ MSM_FN void f_mul_sub(Fp2 &r, const Fp2 &a, const Fp2 &b, const Fp2 &c, const Fp
   fp_mul4(t1, a.c0, b1, a.c1, b0, c.c0, nd1, c.c1, nd0);
   r.c0 = t0;
   r.c1 = t1;
+}
+
+// ------------------------------------------- products by column form (tag) ---
+// What ec.hpp calls: MulSplit is the untagged product of whatever field;
+// MulChain exists over Fp only (the G1 kernels that ask for it).
+template <class F>
+MSM_FN void f_mul(F &r, const F &a, const F &b, MulSplit) { f_mul(r, a, b); }
+template <class F>
+MSM_FN void f_mul_bs(F &r, const F &a, const F &b, MulSplit) { f_mul_bs(r, a, b); }
+template <class F>
+MSM_FN void f_sqr(F &r, const F &a, MulSplit) { f_sqr(r, a); }
+template <class F>
+MSM_FN void f_mul_sub(F &r, const F &a, const F &b, const F &c, const F &d, MulSplit) { f_mul_sub(r, a, b, c, d); }
+template <class F>
+MSM_FN void f_mul_sub_bs(F &r, const F &a, const F &b, const F &c, const F &d, MulSplit) {
+  f_mul_sub_bs(r, a, b, c, d);
+}
+MSM_FN void f_mul(Fp &r, const Fp &a, const Fp &b, MulChain) { fp_mul(r, a, b, MulChain{}); }
+MSM_FN void f_mul_bs(Fp &r, const Fp &a, const Fp &b, MulChain) { fp_mul(r, a, b, MulChain{}); }
+MSM_FN void f_sqr(Fp &r, const Fp &a, MulChain) { fp_sqr(r, a, MulChain{}); }
+MSM_FN void f_mul_sub(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d, MulChain) {
+  Fp nd;
+  fp_neg<4>(nd, d);  // as f_mul_sub; nd first: it dies here, c often does not
+  fp_mul2(r, a, b, nd, c, MulChain{});
+}
+MSM_FN void f_mul_sub_bs(Fp &r, const Fp &a, const Fp &b, const Fp &c, const Fp &d, MulChain) {
+  f_mul_sub(r, a, b, c, d, MulChain{});
 }
 
 }  // namespace msm

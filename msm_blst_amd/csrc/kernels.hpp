@@ -284,6 +284,23 @@ static __global__ void k_iota(uint32_t *a, size_t n) {
 #ifndef MSM_ACC_WAVES
 #define MSM_ACC_WAVES 3
 #endif
+// MSM_ACC_CHAIN (build-time A/B knob): 1 builds the G1 accumulation's madd with
+// the single-chain Montgomery columns (fp.hpp MulChain), 0 with the split ones;
+// same values, other instruction order.  1 measured faster in the 2^20 batch
+// (DESIGN 25 has the counts and the measurements)
+#ifndef MSM_ACC_CHAIN
+#define MSM_ACC_CHAIN 1
+#endif
+template <int G>
+struct AccForm {
+  typedef MulSplit T;
+};
+#if MSM_ACC_CHAIN
+template <>
+struct AccForm<1> {
+  typedef MulChain T;
+};
+#endif
 // The entry stream of schedule position t (AccSched): row k of its wave
 // group's interleaved block (stride 64: one coalesced read per wave step), or,
 // for a group left in bucket order, its run in `sorted` (stride 1).
@@ -339,7 +356,7 @@ __device__ __forceinline__ void accumulate_bucket(const AccSched &S, const PT *_
     }
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
     const bool start = xyzz_is_inf(acc);
-    xyzz_madd(acc, p, (ce >> 31) != 0, fresh);
+    xyzz_madd<F, typename AccForm<G>::T>(acc, p, (ce >> 31) != 0, fresh);
     fresh = start;
   }
 #elif MSM_ACC_PREFETCH
@@ -356,7 +373,7 @@ __device__ __forceinline__ void accumulate_bucket(const AccSched &S, const PT *_
     }
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
     const bool start = xyzz_is_inf(acc);
-    xyzz_madd(acc, p, (ce >> 31) != 0, fresh);
+    xyzz_madd<F, typename AccForm<G>::T>(acc, p, (ce >> 31) != 0, fresh);
     fresh = start;
   }
 #else
@@ -365,7 +382,7 @@ __device__ __forceinline__ void accumulate_bucket(const AccSched &S, const PT *_
     Aff<F> p = ld_point(&pts[e & 0x7fffffffu]);
     if (f_is_zero_exact(p.x) && f_is_zero_exact(p.y)) continue;  // affine infinity (ec_ops.h:717)
     const bool start = xyzz_is_inf(acc);
-    xyzz_madd(acc, p, (e >> 31) != 0, fresh);
+    xyzz_madd<F, typename AccForm<G>::T>(acc, p, (e >> 31) != 0, fresh);
     fresh = start;
   }
 #endif

@@ -78,6 +78,33 @@ __global__ void __launch_bounds__(256, MSM_ACC_WAVES) k_probe_madd(uint32_t *out
   out[t] = s;
 }
 
+// One of each product and of the two G1 point formulas per lane, in the column
+// form CF (fp.hpp MulSplit / MulChain): lane t reads 8 field elements a0..a7 and
+// writes a0 a1, a0^2, a0 a1 + a2 a3, then (a0..a3) as an xyzz point += the
+// affine row (a4, a5) (negated on odd lanes) and += the xyzz point (a4..a7).
+template <class CF>
+__global__ void __launch_bounds__(256) k_form_ops(const Fp *__restrict__ in, Fp *__restrict__ out, size_t lanes) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= lanes) return;
+  const Fp *a = in + t * 8;
+  Fp *o = out + t * 11;
+  Fp r;
+  fp_mul(r, a[0], a[1], CF{});
+  o[0] = r;
+  fp_sqr(r, a[0], CF{});
+  o[1] = r;
+  fp_mul2(r, a[0], a[1], a[2], a[3], CF{});
+  o[2] = r;
+  Xyzz<Fp> q = {a[0], a[1], a[2], a[3]};
+  const Aff<Fp> p = {a[4], a[5]};
+  xyzz_madd<Fp, CF>(q, p, (t & 1) != 0);
+  o[3] = q.x, o[4] = q.y, o[5] = q.zzz, o[6] = q.zz;
+  q = {a[0], a[1], a[2], a[3]};
+  const Xyzz<Fp> b = {a[4], a[5], a[6], a[7]};
+  xyzz_add<Fp, true, CF>(q, b);
+  o[7] = q.x, o[8] = q.y, o[9] = q.zzz, o[10] = q.zz;
+}
+
 template <class L>
 float best_ms(L launch) {
   hipEvent_t e0, e1;
@@ -154,6 +181,21 @@ void valu_probe(int device, double out[4]) {
     out[2] = madd;
     out[3] = total;
   }
+}
+
+// in: lanes x 8 field elements (14 words of 28 bits each), out: lanes x 11
+void form_ops(int device, int form, const uint32_t *in, size_t lanes, uint32_t *out) {
+  DeviceGuard g(device);
+  DevBuf ibuf, obuf;
+  ibuf.ensure(lanes * 8 * sizeof(Fp));
+  obuf.ensure(lanes * 11 * sizeof(Fp));
+  MSM_HIP_CHECK(hipMemcpy(ibuf.p, in, lanes * 8 * sizeof(Fp), hipMemcpyHostToDevice));
+  const dim3 grid((unsigned)((lanes + 255) / 256));
+  if (form) hipLaunchKernelGGL(k_form_ops<MulChain>, grid, dim3(256), 0, 0, ibuf.as<Fp>(), obuf.as<Fp>(), lanes);
+  else hipLaunchKernelGGL(k_form_ops<MulSplit>, grid, dim3(256), 0, 0, ibuf.as<Fp>(), obuf.as<Fp>(), lanes);
+  MSM_HIP_CHECK(hipGetLastError());
+  MSM_HIP_CHECK(hipDeviceSynchronize());
+  MSM_HIP_CHECK(hipMemcpy(out, obuf.p, lanes * 11 * sizeof(Fp), hipMemcpyDeviceToHost));
 }
 
 }  // namespace msm

@@ -24,6 +24,25 @@ __global__ void k_op_fp_mul2(const Fp *a, const Fp *b, Fp *r) {
   fp_mul2(z, x, y, u, v);
   r[t] = z;
 }
+// the same three in the single-chain column form (fp.hpp MulChain)
+__global__ void k_op_fp_mul_chain(const Fp *a, const Fp *b, Fp *r) {
+  const int t = threadIdx.x;
+  Fp x = a[t], y = b[t], z;
+  fp_mul(z, x, y, MulChain{});
+  r[t] = z;
+}
+__global__ void k_op_fp_sqr_chain(const Fp *a, Fp *r) {
+  const int t = threadIdx.x;
+  Fp x = a[t], z;
+  fp_sqr(z, x, MulChain{});
+  r[t] = z;
+}
+__global__ void k_op_fp_mul2_chain(const Fp *a, const Fp *b, Fp *r) {
+  const int t = threadIdx.x;
+  Fp x = a[t], y = b[t], u = a[t + 64], v = b[t + 64], z;
+  fp_mul2(z, x, y, u, v, MulChain{});
+  r[t] = z;
+}
 // G2 on lane pairs (fp2l.hpp): the three products of the lane-pair madd, per lane
 __global__ void k_op_g2l_mul_bs(const Fp2L *a, const Fp2L *b, Fp2L *r) {
   const int t = threadIdx.x;
@@ -66,5 +85,18 @@ __global__ void __launch_bounds__(256) k_op_g2l_add(const Xyzz<Fp2L> *acc, const
   const int t = threadIdx.x;
   Xyzz<Fp2L> q = acc[t];
   xyzz_add(q, b[t]);
+  r[t] = q;
+}
+// G1 madd and general add with single-chain columns
+__global__ void __launch_bounds__(256, 3) k_op_g1_madd_chain(const Xyzz<Fp> *acc, const Aff<Fp> *p, Xyzz<Fp> *r) {
+  const int t = threadIdx.x;
+  Xyzz<Fp> q = acc[t];
+  xyzz_madd<Fp, MulChain>(q, p[t], (t & 1) != 0);
+  r[t] = q;
+}
+__global__ void __launch_bounds__(256, 3) k_op_g1_add_chain(const Xyzz<Fp> *acc, const Xyzz<Fp> *b, Xyzz<Fp> *r) {
+  const int t = threadIdx.x;
+  Xyzz<Fp> q = acc[t];
+  xyzz_add<Fp, true, MulChain>(q, b[t]);
   r[t] = q;
 }

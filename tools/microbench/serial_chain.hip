@@ -6,6 +6,9 @@
 // the next column's first mad; 26 fewer VALU ops, a 392-long dependency chain).
 // fp_mul_col (serial_col.inc, tools/microbench/gen_serial_col.py): the same
 // chain with one asm block per column half (fewer compiler-inserted s_nops).
+// pinned: fp.hpp's fp_mul(r, a, b, MulChain{}), the same single chain with no
+// instruction in asm at all: empty asm statements pin the carry and the next
+// column's operands so that the compiler itself seeds each column with the carry.
 // Register-resident loop of two independent products per lane (the probe's
 // k_probe_fpmul), at 2 / 3 / 4 waves per SIMD; prints Fp-mul/s and checks the
 // two versions agree bit for bit.
@@ -120,7 +123,10 @@ __global__ void __launch_bounds__(256, W) k_rate(uint32_t *out, int iters) {
   b.v[NL - 1] &= 0xffff;
   c.v[NL - 1] &= 0xffff;
   for (int it = 0; it < iters; ++it) {
-    if (SERIAL == 3) {
+    if (SERIAL == 4) {
+      fp_mul(d, a, b, MulChain{});
+      fp_mul(a, c, b, MulChain{});
+    } else if (SERIAL == 3) {
       fp_mul_kara(d, a, b);
       fp_mul_kara(a, c, b);
     } else if (SERIAL == 2) {
@@ -171,19 +177,21 @@ int main() {
   if (hipMalloc(&out, (size_t)cus * 8 * 256 * 4) != hipSuccess) return 1;
   std::vector<uint32_t> h0, h1;
   for (int rep = 0; rep < 2; ++rep) {
-    std::vector<uint32_t> h2, h3;
-    double b2 = rate<0, 2>(out, cus, h0), s2 = rate<1, 2>(out, cus, h1), c2 = rate<2, 2>(out, cus, h2),
-           k2 = rate<3, 2>(out, cus, h3);
-    bool same2 = h0 == h1 && h0 == h2 && h0 == h3;
-    double b3 = rate<0, 3>(out, cus, h0), s3 = rate<1, 3>(out, cus, h1), c3 = rate<2, 3>(out, cus, h2),
-           k3 = rate<3, 3>(out, cus, h3);
-    bool same3 = h0 == h1 && h0 == h2 && h0 == h3;
-    double b4 = rate<0, 4>(out, cus, h0), s4 = rate<1, 4>(out, cus, h1), c4 = rate<2, 4>(out, cus, h2),
-           k4 = rate<3, 4>(out, cus, h3);
-    bool same4 = h0 == h1 && h0 == h2 && h0 == h3;
-    printf("waves/SIMD 2: split %.2f G  serial %.2f G  column-asm %.2f G  karatsuba %.2f G  same %d\n", b2 / 1e9, s2 / 1e9, c2 / 1e9, k2 / 1e9, same2);
-    printf("waves/SIMD 3: split %.2f G  serial %.2f G  column-asm %.2f G  karatsuba %.2f G  same %d\n", b3 / 1e9, s3 / 1e9, c3 / 1e9, k3 / 1e9, same3);
-    printf("waves/SIMD 4: split %.2f G  serial %.2f G  column-asm %.2f G  karatsuba %.2f G  same %d\n", b4 / 1e9, s4 / 1e9, c4 / 1e9, k4 / 1e9, same4);
+    std::vector<uint32_t> h2, h3, h4;
+    double r[3][5];
+    bool same[3];
+    r[0][0] = rate<0, 2>(out, cus, h0), r[0][1] = rate<1, 2>(out, cus, h1), r[0][2] = rate<2, 2>(out, cus, h2),
+    r[0][3] = rate<3, 2>(out, cus, h3), r[0][4] = rate<4, 2>(out, cus, h4);
+    same[0] = h0 == h1 && h0 == h2 && h0 == h3 && h0 == h4;
+    r[1][0] = rate<0, 3>(out, cus, h0), r[1][1] = rate<1, 3>(out, cus, h1), r[1][2] = rate<2, 3>(out, cus, h2),
+    r[1][3] = rate<3, 3>(out, cus, h3), r[1][4] = rate<4, 3>(out, cus, h4);
+    same[1] = h0 == h1 && h0 == h2 && h0 == h3 && h0 == h4;
+    r[2][0] = rate<0, 4>(out, cus, h0), r[2][1] = rate<1, 4>(out, cus, h1), r[2][2] = rate<2, 4>(out, cus, h2),
+    r[2][3] = rate<3, 4>(out, cus, h3), r[2][4] = rate<4, 4>(out, cus, h4);
+    same[2] = h0 == h1 && h0 == h2 && h0 == h3 && h0 == h4;
+    for (int w = 0; w < 3; ++w)
+      printf("waves/SIMD %d: split %.2f G  serial %.2f G  column-asm %.2f G  karatsuba %.2f G  pinned %.2f G  same %d\n",
+             w + 2, r[w][0] / 1e9, r[w][1] / 1e9, r[w][2] / 1e9, r[w][3] / 1e9, r[w][4] / 1e9, same[w]);
   }
   (void)hipFree(out);
   return 0;
