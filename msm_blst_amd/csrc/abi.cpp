@@ -15,6 +15,9 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "../../include/msm_mi355x.h"
 #include "decode.hpp"
@@ -73,6 +76,67 @@ void die(const char *where, const std::exception &e, void *ret = nullptr, size_t
   g_pending = 1;
   if (ret) memset(ret, 0, ret_bytes);
 }
+
+// ---- what the entry points share ----
+// body() -> int under the boundary's catch: a std::exception becomes `code` (the
+// entry point's own: most give MSM_E_HIP, a few MSM_E_ARG) with its message in
+// msm_last_error(), after on_throw() has done the call's own clean-up.
+template <class Body, class OnThrow>
+int guarded(int code, Body body, OnThrow on_throw) {
+  try {
+    return body();
+  } catch (const std::exception &e) {
+    on_throw();
+    return fail(code, e.what());
+  }
+}
+template <class Body>
+int guarded(int code, Body body) {
+  return guarded(code, body, [] {});
+}
+
+// the same for a void blst-named entry point; `where` is its exported name
+template <class Body>
+void blst_guarded(const char *where, void *ret, size_t ret_bytes, Body body) {
+  try {
+    body();
+  } catch (const std::exception &e) {
+    die(where, e, ret, ret_bytes);
+  }
+}
+
+// f(std::integral_constant<int, G>{}) for the group G.  A group other than 1 runs
+// as 2, as in the if / else pairs this replaces; most callers checked it before.
+template <class F>
+decltype(auto) by_group(int group, F f) {
+  if (group == 1) return f(std::integral_constant<int, 1>{});
+  return f(std::integral_constant<int, 2>{});
+}
+
+bool device_ok(int dev) {
+  const int ndev = msm_device_count();
+  return dev >= 0 && dev < ndev;
+}
+int no_device() { return fail(MSM_E_NODEV, "no such HIP device"); }
+
+// on_throw of the bulk calls: a host destination is never left half written
+void zero_host(void *dst, size_t bytes, bool dst_dev) {
+  if (dst && !dst_dev) memset(dst, 0, bytes);
+}
+
+// The status bytes of n items of a bulk call that also counts its failures: the
+// caller's, or a buffer of our own when the caller gave none and wants the count.
+struct StatusBytes {
+  std::vector<uint8_t> own;
+  uint8_t *p;
+  StatusBytes(uint8_t *status, size_t n, bool counted) : p(status) {
+    if (!p && counted) {
+      own.resize(n);
+      p = own.data();
+    }
+  }
+  size_t count_not(size_t n, uint8_t good) const { return n - (size_t)std::count(p, p + n, good); }
+};
 
 template <int G>
 std::unique_ptr<typename EnginePool<Pippenger<G>>::Lease> pippenger_engine(int window) {
@@ -328,17 +392,6 @@ void zero_fill(int dev, void *dst, size_t bytes, bool src_dev, bool dst_dev, hip
 }
 
 // ---- bulk Jacobian -> affine (ref multi_scalar.c:17-62) ----
-// runs: the host source as runs of adjacent points (ptr_walk.hpp), or empty
-// with src_dev set.
-template <int G>
-void points_to_affine(int dev, void *dst, const void *src_dev_ptr,
-                      const std::vector<typename ToAffine<G>::Run> &runs, size_t n, bool src_dev, bool dst_dev,
-                      hipStream_t user) {
-  bulk_run<ToAffine<G>>(dev, G, src_dev, dst_dev, user, [&](ToAffine<G> &e, hipStream_t cs) {
-    e.run(cs, src_dev_ptr, runs, dst, n, src_dev, dst_dev);
-  });
-}
-
 constexpr int kCurrentDevice = -0x7fffffff;  // the blst-style calls: hipGetDevice
 
 bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn) {
@@ -346,6 +399,8 @@ bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn) {
   return x < y + bn && y < x + an;
 }
 
+// runs: the host source as runs of adjacent points (ptr_walk.hpp), or empty
+// with src_dev set.
 template <int G>
 int points_to_affine_checked(int dev, void *dst, const void *src_flat, const void *const *ptrs, size_t n,
                              bool src_dev, bool dst_dev, hipStream_t user) {
@@ -363,28 +418,19 @@ int points_to_affine_checked(int dev, void *dst, const void *src_flat, const voi
     return fail(MSM_E_ARG, "device source not 8-byte aligned");
   }
   if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev == kCurrentDevice ? ndev < 1 : (dev < 0 || dev >= ndev)) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
+  if (dev == kCurrentDevice ? msm_device_count() < 1 : !device_ok(dev)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, n * 96 * G, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
     if (dev == kCurrentDevice) MSM_HIP_CHECK(hipGetDevice(&dev));
-    points_to_affine<G>(dev, dst, src_flat, runs, n, src_dev, dst_dev, user);
+    bulk_run<ToAffine<G>>(dev, G, src_dev, dst_dev, user, [&](ToAffine<G> &e, hipStream_t cs) {
+      e.run(cs, src_flat, runs, dst, n, src_dev, dst_dev);
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (!dst_dev) memset(dst, 0, n * 96 * G);  // never half written
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 // ---- bulk point decoding (ref e1.c:236-351, e2.c:279-410, map_to_g{1,2}.c in_g{1,2}) ----
 // status: n host bytes or NULL.
-template <int G>
-void points_decode(int dev, void *dst, uint8_t *status, const void *src, size_t n, bool serialized, bool check_group,
-                   bool src_dev, bool dst_dev, hipStream_t user) {
-  bulk_run<Decode<G>>(dev, G, src_dev, dst_dev, user, [&](Decode<G> &e, hipStream_t cs) {
-    e.run(cs, src, dst, status, n, serialized, check_group, src_dev, dst_dev);
-  });
-}
-
 int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t *nbad, const void *src, size_t n,
                           int encoding, int flags, bool src_dev, bool dst_dev, hipStream_t user) {
   if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
@@ -402,36 +448,26 @@ int points_decode_checked(int group, int dev, void *dst, uint8_t *status, size_t
     return fail(MSM_E_ARG, "status overlaps the source or the destination");
   if (src_dev && ((uintptr_t)src & 3) != 0) return fail(MSM_E_ARG, "device source not 4-byte aligned");
   if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  std::vector<uint8_t> own;  // nbad without status: counted from a buffer of our own
-  uint8_t *st = status;
-  try {
-    if (!st && nbad) {
-      own.resize(n);
-      st = own.data();
-    }
-    if (group == 1) points_decode<1>(dev, dst, st, src, n, ser, (flags & MSM_DECODE_CHECK_GROUP) != 0, src_dev, dst_dev, user);
-    else points_decode<2>(dev, dst, st, src, n, ser, (flags & MSM_DECODE_CHECK_GROUP) != 0, src_dev, dst_dev, user);
-    if (nbad) *nbad = n - (size_t)std::count(st, st + n, (uint8_t)0);
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    if (!dst_dev) memset(dst, 0, n * aff);  // never half written
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] {
+    zero_host(dst, n * aff, dst_dev);
     if (status) memset(status, 1, n);
     if (nbad) *nbad = n;
-    return fail(MSM_E_HIP, e.what());
-  }
+  };
+  return guarded(MSM_E_HIP, [&] {
+    StatusBytes st(status, n, nbad != nullptr);
+    by_group(group, [&](auto g) {
+      constexpr int G = decltype(g)::value;
+      bulk_run<Decode<G>>(dev, G, src_dev, dst_dev, user, [&](Decode<G> &e, hipStream_t cs) {
+        e.run(cs, src, dst, st.p, n, ser, (flags & MSM_DECODE_CHECK_GROUP) != 0, src_dev, dst_dev);
+      });
+    });
+    if (nbad) *nbad = st.count_not(n, 0);
+    return MSM_OK;
+  }, on_throw);
 }
 
 // ---- bulk point encoding (a loop over ref e1.c:139-234 and the e2.c twins) ----
-template <int G>
-void points_encode(int dev, void *dst, const void *src, size_t n, bool jacobian, bool serialized, bool src_dev,
-                   bool dst_dev, hipStream_t user) {
-  bulk_run<Encode<G>>(dev, G, src_dev, dst_dev, user, [&](Encode<G> &e, hipStream_t cs) {
-    e.run(cs, src, dst, n, jacobian, serialized, src_dev, dst_dev);
-  });
-}
-
 int points_encode_checked(int group, int dev, void *dst, const void *src, size_t n, int src_form, int encoding,
                           int flags, bool src_dev, bool dst_dev, hipStream_t user) {
   if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
@@ -447,16 +483,17 @@ int points_encode_checked(int group, int dev, void *dst, const void *src, size_t
     return fail(MSM_E_ARG, "source and destination overlap");
   if (src_dev && ((uintptr_t)src & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
   if (dst_dev && ((uintptr_t)dst & 3) != 0) return fail(MSM_E_ARG, "device destination not 4-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    if (group == 1) points_encode<1>(dev, dst, src, n, jac, ser, src_dev, dst_dev, user);
-    else points_encode<2>(dev, dst, src, n, jac, ser, src_dev, dst_dev, user);
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, n * enc, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      constexpr int G = decltype(g)::value;
+      bulk_run<Encode<G>>(dev, G, src_dev, dst_dev, user, [&](Encode<G> &e, hipStream_t cs) {
+        e.run(cs, src, dst, n, jac, ser, src_dev, dst_dev);
+      });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (!dst_dev) memset(dst, 0, n * enc);  // never half written
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 // ---- bulk scalar multiplication (a loop over ref e1.c:505-533 blst_p1_mult, e2.c, ec_mult.h) ----
@@ -484,16 +521,14 @@ int points_mult_checked(int group, int dev, void *dst, const void *points, const
     return fail(MSM_E_ARG, "source and destination overlap");
   if (src_dev && ((uintptr_t)points & 7) != 0) return fail(MSM_E_ARG, "device points not 8-byte aligned");
   if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    if (group == 1) points_mult<1>(dev, dst, points, scalars, n, (int)nbits, stride, one, src_dev, dst_dev, user);
-    else points_mult<2>(dev, dst, points, scalars, n, (int)nbits, stride, one, src_dev, dst_dev, user);
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, n * aff, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      points_mult<decltype(g)::value>(dev, dst, points, scalars, n, (int)nbits, stride, one, src_dev, dst_dev, user);
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (!dst_dev) memset(dst, 0, n * aff);  // never half written
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 // ---- segmented sums and MSMs (a loop over ref multi_scalar.c:581-607 / bulk_addition.c:145-164 per point set) ----
@@ -530,27 +565,18 @@ int points_segments_checked(int group, int dev, void *dst, const void *points, c
     return fail(MSM_E_ARG, "source and destination overlap");
   if (src_dev && ((uintptr_t)points & 7) != 0) return fail(MSM_E_ARG, "device points not 8-byte aligned");
   if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    if (group == 1) points_segments<1>(dev, dst, points, scalars, offsets, k, (int)nbits, stride, src_dev, dst_dev, user);
-    else points_segments<2>(dev, dst, points, scalars, offsets, k, (int)nbits, stride, src_dev, dst_dev, user);
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, k * aff, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      points_segments<decltype(g)::value>(dev, dst, points, scalars, offsets, k, (int)nbits, stride, src_dev, dst_dev,
+                                          user);
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (!dst_dev) memset(dst, 0, k * aff);  // never half written
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 // ---- bulk hash-to-curve (a loop over ref map_to_g{1,2}.c hash / encode / map, hash_to_field.c) ----
-template <int G>
-void hash_to_curve(int dev, int mode, void *dst, const void *u, const H2cMsgs &m, const H2cTemplate *tmpl, size_t n,
-                   int count, bool src_dev, bool dst_dev, hipStream_t user) {
-  bulk_run<HashToCurve<G>>(dev, G, src_dev, dst_dev, user, [&](HashToCurve<G> &e, hipStream_t cs) {
-    e.run(cs, mode, u, m, tmpl, dst, n, count, src_dev, dst_dev);
-  });
-}
-
 int hash_to_curve_checked(int group, int dev, int mode, void *dst, const void *u, const void *msgs,
                           const size_t *offsets, size_t msg_len, const void *aug, size_t aug_len, size_t n,
                           const byte *DST, size_t DST_len, int count, bool src_dev, bool dst_dev, hipStream_t user) {
@@ -590,16 +616,17 @@ int hash_to_curve_checked(int group, int dev, int mode, void *dst, const void *u
     h2c_make_template(tmpl, DST, DST_len, (unsigned)(64 * count * group));
   }
   if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    if (group == 1) hash_to_curve<1>(dev, mode, dst, u, m, &tmpl, n, count, src_dev, dst_dev, user);
-    else hash_to_curve<2>(dev, mode, dst, u, m, &tmpl, n, count, src_dev, dst_dev, user);
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, out_bytes, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      constexpr int G = decltype(g)::value;
+      bulk_run<HashToCurve<G>>(dev, G, src_dev, dst_dev, user, [&](HashToCurve<G> &e, hipStream_t cs) {
+        e.run(cs, mode, u, m, &tmpl, dst, n, count, src_dev, dst_dev);
+      });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (!dst_dev) memset(dst, 0, out_bytes);  // never half written
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 // ---- bulk pairings (a loop over ref pairing.c:181-262 miller_loop_n and 371-404 final_exp per pair) ----
@@ -635,15 +662,14 @@ int pairing_checked(int dev, void *dst, uint8_t *is_one, size_t *nfail, const vo
       return fail(MSM_E_ARG, "device points not 8-byte aligned");
   }
   if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  std::vector<uint8_t> own;  // nfail without is_one: counted from a buffer of our own
-  uint8_t *st = is_one;
-  try {
-    if (!st && nfail) {
-      own.resize(k);
-      st = own.data();
-    }
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] {
+    zero_host(dst, k * GT, dst_dev);
+    if (is_one) memset(is_one, 0, k);
+    if (nfail) *nfail = k;
+  };
+  return guarded(MSM_E_HIP, [&] {
+    StatusBytes st(is_one, k, nfail != nullptr);
     std::vector<size_t> single;  // offsets == NULL: one pair per segment
     if (!fe_only && !offsets) {
       single.resize(k + 1);
@@ -651,17 +677,12 @@ int pairing_checked(int dev, void *dst, uint8_t *is_one, size_t *nfail, const vo
       offsets = single.data();
     }
     bulk_run<Pairing>(dev, 0, src_dev, dst_dev, user, [&](Pairing &e, hipStream_t cs) {
-      if (fe_only) e.run_final_exp(cs, src, k, dst, st, src_dev, dst_dev);
-      else e.run(cs, p, q, offsets, k, dst, st, fe, src_dev, dst_dev);
+      if (fe_only) e.run_final_exp(cs, src, k, dst, st.p, src_dev, dst_dev);
+      else e.run(cs, p, q, offsets, k, dst, st.p, fe, src_dev, dst_dev);
     });
-    if (nfail) *nfail = k - (size_t)std::count(st, st + k, (uint8_t)1);
+    if (nfail) *nfail = st.count_not(k, 1);
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (dst && !dst_dev) memset(dst, 0, k * GT);  // never half written
-    if (is_one) memset(is_one, 0, k);
-    if (nfail) *nfail = k;
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 // ---- bulk signature verification (a loop over ref aggregate.c: core_verify, and the
@@ -722,15 +743,13 @@ int sigs_checked(const SigArgs &a) {
   const bool enc = (a.flags & MSM_SIG_ENCODED) != 0;
   if (a.src_dev && (((uintptr_t)a.pks | (uintptr_t)a.sigs) & (enc ? 3 : 7)) != 0)
     return fail(MSM_E_ARG, enc ? "device keys / signatures not 4-byte aligned" : "device keys / signatures not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (a.dev < 0 || a.dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  std::vector<uint8_t> own;  // nfail without status: counted from a buffer of our own
-  uint8_t *st = a.status;
-  try {
-    if (!st) {
-      own.resize(k);
-      st = own.data();
-    }
+  if (!device_ok(a.dev)) return no_device();
+  const auto on_throw = [&] {
+    if (a.status) memset(a.status, SIG_VERIFY_FAIL, k);
+    if (a.nfail) *a.nfail = k;
+  };
+  return guarded(MSM_E_HIP, [&] {
+    StatusBytes st(a.status, k, true);  // (no status: nfail was asked for)
     SigCall c;
     c.mode = a.mode;
     c.encoded = enc;
@@ -749,17 +768,14 @@ int sigs_checked(const SigArgs &a) {
     h2c_make_template(tmpl, a.DST, a.DST_len, (unsigned)(64 * c.count * hg));
     c.tmpl = &tmpl;
     c.o = a.offsets, c.pk = a.pk_offsets, c.k = k, c.src_dev = a.src_dev;
-    if (a.scheme == MSM_SIG_MIN_PK)
-      bulk_run<SigVerify<1>>(a.dev, a.scheme, a.src_dev, false, a.user, [&](SigVerify<1> &e, hipStream_t cs) { e.run(cs, c, st); });
-    else
-      bulk_run<SigVerify<2>>(a.dev, a.scheme, a.src_dev, false, a.user, [&](SigVerify<2> &e, hipStream_t cs) { e.run(cs, c, st); });
-    if (a.nfail) *a.nfail = k - (size_t)std::count(st, st + k, (uint8_t)0);
+    static_assert(MSM_SIG_MIN_PK == 1 && MSM_SIG_MIN_SIG == 2, "SigVerify<G>: G is the group of the public keys");
+    by_group(a.scheme, [&](auto g) {
+      typedef SigVerify<decltype(g)::value> E;
+      bulk_run<E>(a.dev, a.scheme, a.src_dev, false, a.user, [&](E &e, hipStream_t cs) { e.run(cs, c, st.p); });
+    });
+    if (a.nfail) *a.nfail = st.count_not(k, 0);
     return MSM_OK;
-  } catch (const std::exception &e) {
-    if (a.status) memset(a.status, SIG_VERIFY_FAIL, k);
-    if (a.nfail) *a.nfail = k;
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 int points_in_group_checked(int group, int dev, uint8_t *in_group, const void *points, size_t n, bool src_dev,
@@ -769,18 +785,17 @@ int points_in_group_checked(int group, int dev, uint8_t *in_group, const void *p
   if (!in_group || !points) return fail(MSM_E_ARG, "null in_group / points");
   if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
   if (src_dev && ((uintptr_t)points & 7) != 0) return fail(MSM_E_ARG, "device points not 8-byte aligned");
-  const int ndev = msm_device_count();
-  if (dev < 0 || dev >= ndev) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    if (group == 1)
-      bulk_run<GroupScreen<1>>(dev, 1, src_dev, false, user, [&](GroupScreen<1> &e, hipStream_t cs) { e.run(cs, points, in_group, n, src_dev); });
-    else
-      bulk_run<GroupScreen<2>>(dev, 2, src_dev, false, user, [&](GroupScreen<2> &e, hipStream_t cs) { e.run(cs, points, in_group, n, src_dev); });
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] { memset(in_group, 0, n); };
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      constexpr int G = decltype(g)::value;
+      bulk_run<GroupScreen<G>>(dev, G, src_dev, false, user, [&](GroupScreen<G> &e, hipStream_t cs) {
+        e.run(cs, points, in_group, n, src_dev);
+      });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    memset(in_group, 0, n);
-    return fail(MSM_E_HIP, e.what());
-  }
+  }, on_throw);
 }
 
 size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
@@ -788,6 +803,22 @@ size_t blst_window(size_t n) {  // ref multi_scalar.c:268-275
   while (n >>= 1) ++w;
   return w > 12 ? w - 3 : (w > 4 ? w - 2 : (w ? 2 : 1));
 }
+
+// What the four context kinds share: the engine E<group> of one group on `device`.
+template <template <int> class E>
+struct GroupCtx {
+  int group = 1;
+  int device = 0;      // (CHES: the first shard's device)
+  bool ready = false;  // a table was built / set / loaded (mult before that: MSM_E_STATE)
+  std::unique_ptr<E<1>> g1;
+  std::unique_ptr<E<2>> g2;
+  // f(engine of the context's group)
+  template <class F>
+  decltype(auto) with(F f) const {
+    if (group == 1) return f(*g1);
+    return f(*g2);
+  }
+};
 }  // namespace
 
 template <class F>
@@ -800,37 +831,18 @@ void fixed_points(hfp::Aff<F> *out, size_t n, hfp::Jac<F> g) {
   hfp::to_affine_batch(out, j.data(), n);
 }
 
-struct msm_ches_ctx {
-  int group = 1;
-  int device = 0;      // first shard's device
-  bool ready = false;  // a table was built / set / loaded (mult before that: MSM_E_STATE)
-  std::unique_ptr<ChesMulti<1>> g1;  // one shard per device (multi.hpp); one shard = one device
-  std::unique_ptr<ChesMulti<2>> g2;
-};
+// the C tags of include/msm_mi355x.h
+struct msm_ches_ctx : GroupCtx<ChesMulti> {};  // one shard per device (multi.hpp); one shard = one device
 
-struct msm_bgmw_ctx {
-  int group = 1;
-  int device = 0;
-  bool ready = false;
-  std::unique_ptr<Bgmw<1>> g1;
-  std::unique_ptr<Bgmw<2>> g2;
+struct msm_bgmw_ctx : GroupCtx<Bgmw> {
   DevBuf scalars;
 };
 
-struct msm_wbits_ctx {
-  int group = 1;
-  int device = 0;
-  bool ready = false;
-  std::unique_ptr<Wbits<1>> g1;
-  std::unique_ptr<Wbits<2>> g2;
+struct msm_wbits_ctx : GroupCtx<Wbits> {
   DevBuf scalars;
 };
 
-struct msm_ctx {
-  int group = 1;
-  int device = 0;
-  std::unique_ptr<Pippenger<1>> g1;
-  std::unique_ptr<Pippenger<2>> g2;
+struct msm_ctx : GroupCtx<Pippenger> {  // (`ready` unused: a context without points multiplies nothing)
   DevBuf scalars;
   DevBuf decoded;  // msm_ctx_set_points_encoded: the decoded affine points
 };
@@ -917,6 +929,98 @@ static int load_table_file(E &eng, int group, int method, int q_exp, int h, cons
   return MSM_OK;
 }
 
+// ---------------- what the context entry points share ----------------
+// The tail of every *_create: a context C of `group` on `device` around the
+// engine make(integral_constant<G>) builds.  *ctx is written on success only;
+// `code` is what a throwing constructor gives.
+template <class C, class Make>
+int create_ctx(C **ctx, int group, int device, int code, Make make) {
+  return guarded(code, [&] {
+    auto c = std::make_unique<C>();
+    c->group = group;
+    c->device = device;
+    if (group == 1) c->g1 = make(std::integral_constant<int, 1>{});
+    else c->g2 = make(std::integral_constant<int, 2>{});
+    *ctx = c.release();
+    return MSM_OK;
+  });
+}
+
+// build_table / set_table / precompute: set(engine) with the context not ready
+// while it runs, and ready after it only if it did not throw
+template <class C, class Set>
+int set_table_ctx(C *ctx, Set set) {
+  return guarded(MSM_E_HIP, [&] {
+    ctx->ready = false;
+    ctx->with(set);
+    ctx->ready = true;
+    return MSM_OK;
+  });
+}
+
+template <class C>
+int get_table_ctx(C *ctx, void *out, size_t first, size_t count, int code) {
+  if (!ctx || (!out && count)) return fail(MSM_E_ARG, "bad args");
+  return guarded(code, [&] {
+    ctx->with([&](auto &e) { e.get_table(out, first, count, (hipStream_t)0); });
+    return MSM_OK;
+  });
+}
+
+// save_table / load_table: `method` and qh(engine) = {q_exp, h} go into / are
+// checked against the file's header
+template <class C, class QH>
+int save_table_ctx(C *ctx, const char *path, int method, QH qh) {
+  if (!ctx || !path) return fail(MSM_E_ARG, "bad args");
+  return guarded(MSM_E_HIP, [&] {
+    DeviceGuard g(ctx->device);
+    return ctx->with([&](auto &e) {
+      const std::pair<int, int> p = qh(e);
+      return save_table_file(e, ctx->group, method, p.first, p.second, path);
+    });
+  });
+}
+template <class C, class QH>
+int load_table_ctx(C *ctx, const char *path, int method, QH qh) {
+  if (!ctx || !path) return fail(MSM_E_ARG, "bad args");
+  return guarded(MSM_E_HIP, [&] {
+    DeviceGuard g(ctx->device);
+    ctx->ready = false;
+    const int rc = ctx->with([&](auto &e) {
+      const std::pair<int, int> p = qh(e);
+      return load_table_file(e, ctx->group, method, p.first, p.second, path);
+    });
+    ctx->ready = rc == MSM_OK;
+    return rc;
+  });
+}
+
+// `count` results of the engine's group: run(out) fills blst Jacobians, which
+// are then copied to the caller's ret
+template <template <int> class E, int G, class Run>
+void mult_out(E<G> &, void *ret, size_t count, Run run) {
+  typedef hfp::Jac<typename HostField<G>::F> J;
+  J one;
+  std::vector<J> many(count > 1 ? count : 0);  // (one result: no allocation)
+  J *out = count > 1 ? many.data() : &one;
+  run(out);
+  memcpy(ret, out, count * sizeof(J));
+}
+
+// the scalars of a single-set mult on the device: host scalars are copied to
+// the context's buffer on `s`, device scalars pass through
+const uint8_t *stage_scalars(DevBuf &buf, const byte *scalars, size_t bytes, bool on_device, hipStream_t s) {
+  if (on_device || !bytes) return scalars;
+  buf.ensure(bytes + 16);
+  MSM_HIP_CHECK(hipMemcpyAsync(buf.p, scalars, bytes, hipMemcpyHostToDevice, s));
+  return buf.as<uint8_t>();
+}
+
+void phase_times_out(const PhaseTimes &t, float out[6]) {
+  const float v[6] = {t.digits, t.sort, t.accumulate, t.reduce, t.finalize, t.total};
+  memcpy(out, v, sizeof v);
+}
+
 }  // namespace
 
 extern "C" {
@@ -924,42 +1028,24 @@ extern "C" {
 size_t blst_p1s_mult_pippenger_scratch_sizeof(size_t npoints) { return sizeof(blst_p1xyzz) << (blst_window(npoints) - 1); }
 size_t blst_p2s_mult_pippenger_scratch_sizeof(size_t npoints) { return sizeof(blst_p2xyzz) << (blst_window(npoints) - 1); }
 
-void blst_p1s_mult_pippenger(blst_p1 *ret, const blst_p1_affine *const points[], size_t npoints,
-                             const byte *const scalars[], size_t nbits, limb_t *scratch) {
-  (void)scratch;
-  try {
-    mult_pippenger<1>(ret, (const void *const *)points, npoints, scalars, nbits);
-  } catch (const std::exception &e) {
-    die("blst_p1s_mult_pippenger", e, ret, sizeof(*ret));
+#define MSM_PIPPENGER_ENTRIES(g)                                                                                  \
+  void blst_p##g##s_mult_pippenger(blst_p##g *ret, const blst_p##g##_affine *const points[], size_t npoints,      \
+                                   const byte *const scalars[], size_t nbits, limb_t *scratch) {                  \
+    (void)scratch;                                                                                                \
+    blst_guarded("blst_p" #g "s_mult_pippenger", ret, sizeof(*ret),                                               \
+                 [&] { mult_pippenger<g>(ret, (const void *const *)points, npoints, scalars, nbits); });          \
+  }                                                                                                               \
+  void blst_p##g##s_tile_pippenger(blst_p##g *ret, const blst_p##g##_affine *const points[], size_t npoints,      \
+                                   const byte *const scalars[], size_t nbits, limb_t *scratch, size_t bit0,       \
+                                   size_t window) {                                                               \
+    (void)scratch;                                                                                                \
+    blst_guarded("blst_p" #g "s_tile_pippenger", ret, sizeof(*ret), [&] {                                         \
+      tile_pippenger<g>(ret, (const void *const *)points, npoints, scalars, nbits, bit0, window);                 \
+    });                                                                                                           \
   }
-}
-void blst_p2s_mult_pippenger(blst_p2 *ret, const blst_p2_affine *const points[], size_t npoints,
-                             const byte *const scalars[], size_t nbits, limb_t *scratch) {
-  (void)scratch;
-  try {
-    mult_pippenger<2>(ret, (const void *const *)points, npoints, scalars, nbits);
-  } catch (const std::exception &e) {
-    die("blst_p2s_mult_pippenger", e, ret, sizeof(*ret));
-  }
-}
-void blst_p1s_tile_pippenger(blst_p1 *ret, const blst_p1_affine *const points[], size_t npoints,
-                             const byte *const scalars[], size_t nbits, limb_t *scratch, size_t bit0, size_t window) {
-  (void)scratch;
-  try {
-    tile_pippenger<1>(ret, (const void *const *)points, npoints, scalars, nbits, bit0, window);
-  } catch (const std::exception &e) {
-    die("blst_p1s_tile_pippenger", e, ret, sizeof(*ret));
-  }
-}
-void blst_p2s_tile_pippenger(blst_p2 *ret, const blst_p2_affine *const points[], size_t npoints,
-                             const byte *const scalars[], size_t nbits, limb_t *scratch, size_t bit0, size_t window) {
-  (void)scratch;
-  try {
-    tile_pippenger<2>(ret, (const void *const *)points, npoints, scalars, nbits, bit0, window);
-  } catch (const std::exception &e) {
-    die("blst_p2s_tile_pippenger", e, ret, sizeof(*ret));
-  }
-}
+MSM_PIPPENGER_ENTRIES(1)
+MSM_PIPPENGER_ENTRIES(2)
+#undef MSM_PIPPENGER_ENTRIES
 
 // ---- blst-level CHES / BGMW95 entry points ----
 size_t blst_p1s_mult_pippenger_scratch_sizeof_CHES(size_t window) { return sizeof(blst_p1xyzz) * (window / 2); }
@@ -999,13 +1085,11 @@ MSM_XYZZ_HELPERS(2, hfp::Fp2)
                                                          int bucket_set_ascend[], size_t bucket_set_size,         \
                                                          int d_max) {                                             \
     (void)d_max;                                                                                                  \
-    try {                                                                                                         \
+    blst_guarded("blst_p" #g "_integrate_buckets_accumulation_d_CHES", out, sizeof(*out), [&] {                   \
       std::vector<uint32_t> w(bucket_set_size);                                                                   \
       for (size_t k = 0; k < bucket_set_size; ++k) w[k] = (uint32_t)std::max(bucket_set_ascend[k], 0);           \
       weighted_bucket_sum<g>(out, buckets, bucket_set_size, w.data());                                            \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "_integrate_buckets_accumulation_d_CHES", e, out, sizeof(*out));                                               \
-    }                                                                                                             \
+    });                                                                                                           \
   }                                                                                                               \
   void blst_p##g##_construct_nh_scalars_nh_points(int nh_scalars[], unsigned char booth_signs[],                  \
                                                   blst_p##g##_affine *nh_points_ptr[], const size_t npoints,     \
@@ -1023,45 +1107,37 @@ MSM_XYZZ_HELPERS(2, hfp::Fp2)
                                          blst_p##g##xyzz buckets[], int bucket_set_ascend[],                      \
                                          int bucket_value_to_its_index[], size_t bucket_set_size, int d_max) {    \
     (void)d_max;                                                                                                  \
-    try {                                                                                                         \
+    blst_guarded("blst_p" #g "_tile_pippenger_d_CHES", ret, sizeof(*ret), [&] {                                   \
       tile_d_ches<g>(ret, (const void *const *)points, npoints, scalars, booth_signs, buckets, bucket_set_ascend, \
                      bucket_value_to_its_index, bucket_set_size);                                                 \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "_tile_pippenger_d_CHES", e, ret, sizeof(*ret));                                                               \
-    }                                                                                                             \
+    });                                                                                                           \
   }                                                                                                               \
   void blst_p##g##_tile_pippenger_d_CHES_noindexhash(                                                             \
       blst_p##g *ret, const blst_p##g##_affine *const points[], size_t npoints, const int scalars[],               \
       const unsigned char booth_signs[], blst_p##g##xyzz buckets[], int bucket_set_ascend[],                      \
       size_t bucket_set_size, int d_max) {                                                                        \
     (void)d_max;                                                                                                  \
-    try {                                                                                                         \
+    blst_guarded("blst_p" #g "_tile_pippenger_d_CHES_noindexhash", ret, sizeof(*ret), [&] {                       \
       tile_d_ches_noindex<g>(ret, (const void *const *)points, npoints, scalars, booth_signs, buckets,            \
                              bucket_set_ascend, bucket_set_size);                                                 \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "_tile_pippenger_d_CHES_noindexhash", e, ret, sizeof(*ret));                                                   \
-    }                                                                                                             \
+    });                                                                                                           \
   }                                                                                                               \
   void blst_p##g##_tile_pippenger_CHES_prefetch_2step_ahead_input_std_scalar(                                     \
       blst_p##g *ret, const blst_p##g##_affine table[], size_t npoints, int scalars[],                            \
       digit_decomposition H[], blst_p##g##xyzz buckets[], int bucket_set_ascend[],                                \
       int bucket_value_to_its_index[], size_t bucket_set_size, int d_max) {                                       \
     (void)d_max;                                                                                                  \
-    try {                                                                                                         \
+    blst_guarded("blst_p" #g "_tile_pippenger_CHES_prefetch_2step_ahead_input_std_scalar", ret, sizeof(*ret), [&] { \
       tile_ches_std<g>(ret, table, npoints, scalars, H, buckets, bucket_set_ascend, bucket_value_to_its_index,    \
                        bucket_set_size);                                                                          \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "_tile_pippenger_CHES_prefetch_2step_ahead_input_std_scalar", e, ret, sizeof(*ret));                           \
-    }                                                                                                             \
+    });                                                                                                           \
   }                                                                                                               \
   void blst_p##g##_tile_pippenger_BGMW95(blst_p##g *ret, const blst_p##g##_affine *const points[], size_t npoints, \
                                          const int scalars[], const unsigned char booth_signs[],                  \
                                          blst_p##g##xyzz buckets[], size_t q_exponent) {                          \
-    try {                                                                                                         \
+    blst_guarded("blst_p" #g "_tile_pippenger_BGMW95", ret, sizeof(*ret), [&] {                                   \
       tile_bgmw95<g>(ret, (const void *const *)points, npoints, scalars, booth_signs, buckets, q_exponent);       \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "_tile_pippenger_BGMW95", e, ret, sizeof(*ret));                                                               \
-    }                                                                                                             \
+    });                                                                                                           \
   }
 MSM_CHES_ENTRIES(1)
 MSM_CHES_ENTRIES(2)
@@ -1072,11 +1148,8 @@ MSM_CHES_ENTRIES(2)
 // the previous point
 #define MSM_POINTS_ADD(g)                                                                                         \
   void blst_p##g##s_add(blst_p##g *ret, const blst_p##g##_affine *const points[], size_t npoints) {             \
-    try {                                                                                                         \
-      points_add<g>(ret, (const void *const *)points, npoints);                                                   \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "s_add", e, ret, sizeof(*ret));                                                                                \
-    }                                                                                                             \
+    blst_guarded("blst_p" #g "s_add", ret, sizeof(*ret),                                                          \
+                 [&] { points_add<g>(ret, (const void *const *)points, npoints); });                              \
   }
 MSM_POINTS_ADD(1)
 MSM_POINTS_ADD(2)
@@ -1089,12 +1162,10 @@ MSM_POINTS_ADD(2)
   }                                                                                                               \
   void blst_p##g##s_mult_wbits_precompute(blst_p##g##_affine table[], size_t wbits,                              \
                                           const blst_p##g##_affine *const points[], size_t npoints) {            \
-    try {                                                                                                         \
-      wbits_precompute<g>(table, wbits, (const void *const *)points, npoints);                                    \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "s_mult_wbits_precompute", e, table,                                                        \
-          blst_p##g##s_mult_wbits_precompute_sizeof(wbits, npoints)); /* no half-written table */                \
-    }                                                                                                             \
+    /* no half-written table: all of it is zeroed (no points: nothing is written and nothing throws) */          \
+    blst_guarded("blst_p" #g "s_mult_wbits_precompute", table,                                                    \
+                 npoints ? blst_p##g##s_mult_wbits_precompute_sizeof(wbits, npoints) : 0,                         \
+                 [&] { wbits_precompute<g>(table, wbits, (const void *const *)points, npoints); });               \
   }                                                                                                               \
   size_t blst_p##g##s_mult_wbits_scratch_sizeof(size_t npoints) {                                                \
     return sizeof(blst_p##g) * (npoints < scratch_pts ? npoints : scratch_pts);                                   \
@@ -1102,11 +1173,8 @@ MSM_POINTS_ADD(2)
   void blst_p##g##s_mult_wbits(blst_p##g *ret, const blst_p##g##_affine table[], size_t wbits, size_t npoints,   \
                                const byte *const scalars[], size_t nbits, limb_t *scratch) {                      \
     (void)scratch;                                                                                                \
-    try {                                                                                                         \
-      wbits_mult<g>(ret, table, wbits, npoints, scalars, nbits);                                                  \
-    } catch (const std::exception &e) {                                                                           \
-      die("blst_p" #g "s_mult_wbits", e, ret, sizeof(*ret));                                                                         \
-    }                                                                                                             \
+    blst_guarded("blst_p" #g "s_mult_wbits", ret, sizeof(*ret),                                                   \
+                 [&] { wbits_mult<g>(ret, table, wbits, npoints, scalars, nbits); });                             \
   }
 MSM_WBITS_ENTRIES(1, 8192)  /* SCRATCH_SZ of ref multi_scalar.c:78 */
 MSM_WBITS_ENTRIES(2, 4096)
@@ -1131,12 +1199,11 @@ int msm_points_to_affine(int group, int device, void *dst, const void *src, size
   if (npoints == 0) return MSM_OK;
   if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
   if (npoints > ((size_t)1 << 40)) return fail(MSM_E_ARG, "npoints out of range");
-  if (device == kCurrentDevice) return fail(MSM_E_NODEV, "no such HIP device");
-  if (group == 1)
-    return points_to_affine_checked<1>(device, dst, src, nullptr, npoints, src_on_device != 0, dst_on_device != 0,
-                                       (hipStream_t)hip_stream);
-  return points_to_affine_checked<2>(device, dst, src, nullptr, npoints, src_on_device != 0, dst_on_device != 0,
-                                     (hipStream_t)hip_stream);
+  if (device == kCurrentDevice) return no_device();
+  return by_group(group, [&](auto g) {
+    return points_to_affine_checked<decltype(g)::value>(device, dst, src, nullptr, npoints, src_on_device != 0,
+                                                        dst_on_device != 0, (hipStream_t)hip_stream);
+  });
 }
 
 int msm_to_affine_levels(size_t npoints) { return (int)ta_levels(std::min(npoints, ta_chunk())).size(); }
@@ -1338,13 +1405,10 @@ size_t msm_set_engine_cache_limit(size_t bytes) {
 
 int msm_register_host_table(int group, const void *rows, size_t nrows) {
   if ((group != 1 && group != 2) || !rows || !nrows) return fail(MSM_E_ARG, "bad group / rows");
-  try {
-    if (group == 1) register_host_table<1>(rows, nrows);
-    else register_host_table<2>(rows, nrows);
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) { register_host_table<decltype(g)::value>(rows, nrows); });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_unregister_host_table(const void *rows) {
@@ -1360,52 +1424,36 @@ int msm_device_count(void) {
 
 int msm_valu_probe(int device, double out[4]) {
   if (!out) return fail(MSM_E_ARG, "null out");
-  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
+  if (!device_ok(device)) return no_device();
+  return guarded(MSM_E_HIP, [&] {
     valu_probe(device, out);
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_fp_form_ops(int device, int form, const uint32_t *in, size_t lanes, uint32_t *out) {
   if (!in || !out || !lanes || (form != 0 && form != 1)) return fail(MSM_E_ARG, "bad in / out / lanes / form");
-  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
+  if (!device_ok(device)) return no_device();
+  return guarded(MSM_E_HIP, [&] {
     form_ops(device, form, in, lanes, out);
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_ctx_create(msm_ctx **ctx, int group, int device, int window_bits) {
   if (!ctx || (group != 1 && group != 2)) return fail(MSM_E_ARG, "bad ctx/group");
-  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    auto c = std::make_unique<msm_ctx>();
-    c->group = group;
-    c->device = device;
-    int wb = window_bits > 0 ? window_bits : 16;
-    if (group == 1) c->g1 = std::make_unique<Pippenger<1>>(device, wb);
-    else c->g2 = std::make_unique<Pippenger<2>>(device, wb);
-    *ctx = c.release();
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  if (!device_ok(device)) return no_device();
+  const int wb = window_bits > 0 ? window_bits : 16;
+  return create_ctx(ctx, group, device, MSM_E_HIP,
+                    [&](auto g) { return std::make_unique<Pippenger<decltype(g)::value>>(device, wb); });
 }
 
 int msm_ctx_set_points(msm_ctx *ctx, const void *points, size_t n, int on_device, void *stream) {
   if (!ctx || (!points && n)) return fail(MSM_E_ARG, "bad args");
-  try {
-    if (ctx->group == 1) ctx->g1->set_points(points, n, on_device != 0, (hipStream_t)stream);
-    else ctx->g2->set_points(points, n, on_device != 0, (hipStream_t)stream);
+  return guarded(MSM_E_HIP, [&] {
+    ctx->with([&](auto &e) { e.set_points(points, n, on_device != 0, (hipStream_t)stream); });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_ctx_set_points_encoded(msm_ctx *ctx, const void *src, size_t n, int encoding, int flags, int src_on_device,
@@ -1413,13 +1461,13 @@ int msm_ctx_set_points_encoded(msm_ctx *ctx, const void *src, size_t n, int enco
   if (!ctx || (!src && n)) return fail(MSM_E_ARG, "bad args");
   if (n == 0) return msm_ctx_set_points(ctx, nullptr, 0, 1, stream);
   std::vector<uint8_t> st;
-  try {
+  const int allocated = guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     st.resize(n);
     ctx->decoded.ensure(n * 96 * (size_t)ctx->group);
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+    return MSM_OK;
+  });
+  if (allocated != MSM_OK) return allocated;
   const int rc = points_decode_checked(ctx->group, ctx->device, ctx->decoded.p, st.data(), nullptr, src, n, encoding,
                                        flags, src_on_device != 0, true, (hipStream_t)stream);
   if (rc != MSM_OK) return rc;
@@ -1434,39 +1482,25 @@ int msm_ctx_set_points_encoded(msm_ctx *ctx, const void *src, size_t n, int enco
 int msm_ctx_mult(msm_ctx *ctx, void *ret, const byte *scalars, size_t stride, size_t nbits, int on_device,
                  void *stream) {
   if (!ctx || !ret || nbits == 0 || nbits > 256 || stride < (nbits + 7) / 8) return fail(MSM_E_ARG, "bad args");
-  try {
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    size_t n = ctx->group == 1 ? ctx->g1->npoints() : ctx->g2->npoints();
-    const uint8_t *d = scalars;
-    if (!on_device && n) {
-      ctx->scalars.ensure(n * stride + 16);
-      MSM_HIP_CHECK(hipMemcpyAsync(ctx->scalars.p, scalars, n * stride, hipMemcpyHostToDevice, s));
-      d = ctx->scalars.as<uint8_t>();
-    }
-    if (ctx->group == 1) {
-      hfp::Jac<hfp::Fp> out;
-      ctx->g1->run(s, d, stride, (int)nbits, &out);
-      memcpy(ret, &out, sizeof out);
-    } else {
-      hfp::Jac<hfp::Fp2> out;
-      ctx->g2->run(s, d, stride, (int)nbits, &out);
-      memcpy(ret, &out, sizeof out);
-    }
+    ctx->with([&](auto &e) {
+      const uint8_t *d = stage_scalars(ctx->scalars, scalars, e.npoints() * stride, on_device != 0, s);
+      mult_out(e, ret, 1, [&](auto *out) { e.run(s, d, stride, (int)nbits, out); });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_ctx_mult_batch(msm_ctx *ctx, void *rets, const byte *scalars, size_t stride, size_t set_stride, size_t nbits,
                        size_t count, int on_device, void *stream) {
   if (!ctx || (!rets && count) || nbits == 0 || nbits > 256 || stride < (nbits + 7) / 8)
     return fail(MSM_E_ARG, "bad args");
-  try {
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = ctx->group == 1 ? ctx->g1->npoints() : ctx->g2->npoints();
+    const size_t n = ctx->with([](auto &e) { return e.npoints(); });
     const uint8_t *d = scalars;
     if (!on_device && n && count) {  // the sets, packed, in one upload
       ctx->scalars.ensure(count * n * stride + 16);
@@ -1476,37 +1510,22 @@ int msm_ctx_mult_batch(msm_ctx *ctx, void *rets, const byte *scalars, size_t str
       d = ctx->scalars.as<uint8_t>();
       set_stride = n * stride;
     }
-    if (ctx->group == 1) {
-      std::vector<hfp::Jac<hfp::Fp>> out(count);
-      ctx->g1->run_batch(s, d, stride, set_stride, count, (int)nbits, out.data());
-      memcpy(rets, out.data(), count * sizeof(out[0]));
-    } else {
-      std::vector<hfp::Jac<hfp::Fp2>> out(count);
-      ctx->g2->run_batch(s, d, stride, set_stride, count, (int)nbits, out.data());
-      memcpy(rets, out.data(), count * sizeof(out[0]));
-    }
+    ctx->with([&](auto &e) {
+      mult_out(e, rets, count, [&](auto *out) { e.run_batch(s, d, stride, set_stride, count, (int)nbits, out); });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_ctx_set_profiling(msm_ctx *ctx, int on) {
   if (!ctx) return fail(MSM_E_ARG, "null ctx");
-  if (ctx->group == 1) ctx->g1->set_profiling(on != 0);
-  else ctx->g2->set_profiling(on != 0);
+  ctx->with([&](auto &e) { e.set_profiling(on != 0); });
   return MSM_OK;
 }
 
 int msm_ctx_phase_times(const msm_ctx *ctx, float out[6]) {
   if (!ctx || !out) return fail(MSM_E_ARG, "null");
-  const PhaseTimes &t = ctx->group == 1 ? ctx->g1->times() : ctx->g2->times();
-  out[0] = t.digits;
-  out[1] = t.sort;
-  out[2] = t.accumulate;
-  out[3] = t.reduce;
-  out[4] = t.finalize;
-  out[5] = t.total;
+  phase_times_out(ctx->with([](auto &e) -> const PhaseTimes & { return e.times(); }), out);
   return MSM_OK;
 }
 
@@ -1525,22 +1544,19 @@ int msm_ches_params(int n_exp, int beta, int out[9]) {
   return MSM_OK;
 }
 
+// The tail of the CHES creates: one shard per entry of devices[0 .. ndev); the
+// context's device is the first.
+static int ches_create(msm_ches_ctx **ctx, int group, const int *devices, int ndev, const int v[9]) {
+  const ChesParams p{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+  return create_ctx(ctx, group, devices[0], MSM_E_HIP, [&](auto g) {
+    return std::make_unique<ChesMulti<decltype(g)::value>>(std::vector<int>(devices, devices + ndev), p);
+  });
+}
+
 int msm_ches_ctx_create_params(msm_ches_ctx **ctx, int group, int device, const int v[9]) {
   if (!ctx || !v || (group != 1 && group != 2)) return fail(MSM_E_ARG, "bad ctx/group/params");
-  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
-  ChesParams p{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
-  try {
-    auto c = std::make_unique<msm_ches_ctx>();
-    c->group = group;
-    c->device = device;
-    const std::vector<int> devs{device};
-    if (group == 1) c->g1 = std::make_unique<ChesMulti<1>>(devs, p);
-    else c->g2 = std::make_unique<ChesMulti<2>>(devs, p);
-    *ctx = c.release();
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  if (!device_ok(device)) return no_device();
+  return ches_create(ctx, group, &device, 1, v);
 }
 
 int msm_ches_ctx_create(msm_ches_ctx **ctx, int group, int device, int n_exp, int beta) {
@@ -1555,97 +1571,57 @@ int msm_ches_ctx_create_multi(msm_ches_ctx **ctx, int group, const int *devices,
   int v[9];
   int rc = msm_ches_params(n_exp, beta, v);
   if (rc) return rc;
-  const int have = msm_device_count();
-  std::vector<int> devs(devices, devices + ndev);
-  for (int d : devs)
-    if (d < 0 || d >= have) return fail(MSM_E_NODEV, "no such HIP device");
-  ChesParams p{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
-  try {
-    auto c = std::make_unique<msm_ches_ctx>();
-    c->group = group;
-    c->device = devs[0];
-    if (group == 1) c->g1 = std::make_unique<ChesMulti<1>>(devs, p);
-    else c->g2 = std::make_unique<ChesMulti<2>>(devs, p);
-    *ctx = c.release();
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  for (int i = 0; i < ndev; ++i)
+    if (!device_ok(devices[i])) return no_device();
+  return ches_create(ctx, group, devices, ndev, v);
 }
 
 int msm_ches_ctx_shards(const msm_ches_ctx *ctx) {
-  if (!ctx) return 0;
-  return (int)(ctx->group == 1 ? ctx->g1->nshards() : ctx->g2->nshards());
+  return ctx ? (int)ctx->with([](auto &e) { return e.nshards(); }) : 0;
 }
 
-#define CHES_DISPATCH(ctx, CALL) ((ctx)->group == 1 ? (ctx)->g1->CALL : (ctx)->g2->CALL)
-
-int msm_ches_ctx_rccl_exchange(const msm_ches_ctx *ctx) { return ctx ? (int)CHES_DISPATCH(ctx, rccl_exchange()) : 0; }
+int msm_ches_ctx_rccl_exchange(const msm_ches_ctx *ctx) {
+  return ctx ? (int)ctx->with([](auto &e) { return e.rccl_exchange(); }) : 0;
+}
 
 // several engines take host memory only (each device gets its own slice); shards
 // merged into one engine on one device (multi.hpp) take device memory like a
 // single-device context
 static bool multi_device_arg(const msm_ches_ctx *ctx, int on_device) {
-  return on_device && (ctx->group == 1 ? ctx->g1->engines() : ctx->g2->engines()) > 1;
+  return on_device && ctx->with([](auto &e) { return e.engines(); }) > 1;
 }
 
 int msm_ches_ctx_build_table(msm_ches_ctx *ctx, const void *pts, size_t n, int on_device, void *stream) {
   if (!ctx || (!pts && n)) return fail(MSM_E_ARG, "bad args");
   if (multi_device_arg(ctx, on_device)) return fail(MSM_E_ARG, "a multi-device context takes host points");
-  try {
-    ctx->ready = false;
-    CHES_DISPATCH(ctx, build_table(pts, n, on_device != 0, (hipStream_t)stream));
-    ctx->ready = true;
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return set_table_ctx(ctx, [&](auto &e) { e.build_table(pts, n, on_device != 0, (hipStream_t)stream); });
 }
 
 int msm_ches_ctx_set_table(msm_ches_ctx *ctx, const void *tab, size_t n, int on_device, void *stream) {
   if (!ctx || (!tab && n)) return fail(MSM_E_ARG, "bad args");
   if (multi_device_arg(ctx, on_device)) return fail(MSM_E_ARG, "a multi-device context takes a host table");
-  try {
-    ctx->ready = false;
-    CHES_DISPATCH(ctx, set_table(tab, n, on_device != 0, (hipStream_t)stream));
-    ctx->ready = true;
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return set_table_ctx(ctx, [&](auto &e) { e.set_table(tab, n, on_device != 0, (hipStream_t)stream); });
 }
 
 int msm_ches_ctx_get_table(msm_ches_ctx *ctx, void *out, size_t first, size_t count) {
-  if (!ctx || (!out && count)) return fail(MSM_E_ARG, "bad args");
-  try {
-    CHES_DISPATCH(ctx, get_table(out, first, count, (hipStream_t)0));
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return get_table_ctx(ctx, out, first, count, MSM_E_HIP);
 }
 
+// (the CHES mults hand the scalars to the engine where they are: host scalars
+// are staged per shard, or set by set inside the pipeline, Ches::run_batch)
 int msm_ches_ctx_mult(msm_ches_ctx *ctx, void *ret, const byte *scalars, size_t stride, int on_device,
                       void *stream) {
   if (!ctx || !ret || stride < 32) return fail(MSM_E_ARG, "bad args (stride must be >= 32)");
   if (!ctx->ready) return fail(MSM_E_STATE, "no table: build_table, set_table or load_table first");
   if (multi_device_arg(ctx, on_device)) return fail(MSM_E_ARG, "a multi-device context takes host scalars");
-  try {
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    if (ctx->group == 1) {
-      hfp::Jac<hfp::Fp> out;
-      ctx->g1->run(s, scalars, stride, on_device != 0, &out);
-      memcpy(ret, &out, sizeof out);
-    } else {
-      hfp::Jac<hfp::Fp2> out;
-      ctx->g2->run(s, scalars, stride, on_device != 0, &out);
-      memcpy(ret, &out, sizeof out);
-    }
+    ctx->with([&](auto &e) {
+      mult_out(e, ret, 1, [&](auto *out) { e.run(s, scalars, stride, on_device != 0, out); });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_ches_ctx_mult_batch(msm_ches_ctx *ctx, void *rets, const byte *scalars, size_t stride, size_t set_stride,
@@ -1653,209 +1629,118 @@ int msm_ches_ctx_mult_batch(msm_ches_ctx *ctx, void *rets, const byte *scalars, 
   if (!ctx || (!rets && count) || stride < 32) return fail(MSM_E_ARG, "bad args (stride must be >= 32)");
   if (!ctx->ready) return fail(MSM_E_STATE, "no table: build_table, set_table or load_table first");
   if (multi_device_arg(ctx, on_device)) return fail(MSM_E_ARG, "a multi-device context takes host scalars");
-  try {
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    // host scalars are streamed set by set inside the pipeline (Ches::run_batch)
     const bool on_host = !on_device;
-    if (ctx->group == 1) {
-      std::vector<hfp::Jac<hfp::Fp>> out(count);
-      ctx->g1->run_batch(s, scalars, stride, set_stride, count, out.data(), on_host);
-      memcpy(rets, out.data(), count * sizeof(out[0]));
-    } else {
-      std::vector<hfp::Jac<hfp::Fp2>> out(count);
-      ctx->g2->run_batch(s, scalars, stride, set_stride, count, out.data(), on_host);
-      memcpy(rets, out.data(), count * sizeof(out[0]));
-    }
+    ctx->with([&](auto &e) {
+      mult_out(e, rets, count, [&](auto *out) { e.run_batch(s, scalars, stride, set_stride, count, out, on_host); });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_ches_ctx_set_profiling(msm_ches_ctx *ctx, int on) {
   if (!ctx) return fail(MSM_E_ARG, "null ctx");
-  CHES_DISPATCH(ctx, set_profiling(on != 0));
+  ctx->with([&](auto &e) { e.set_profiling(on != 0); });
   return MSM_OK;
 }
 
 int msm_ches_ctx_phase_times(const msm_ches_ctx *ctx, float out[6]) {
   if (!ctx || !out) return fail(MSM_E_ARG, "null");
-  const PhaseTimes &t = CHES_DISPATCH(ctx, front().times());
-  const float v[6] = {t.digits, t.sort, t.accumulate, t.reduce, t.finalize, t.total};
-  memcpy(out, v, sizeof v);
+  phase_times_out(ctx->with([](auto &e) -> const PhaseTimes & { return e.front().times(); }), out);
   return MSM_OK;
 }
 
-size_t msm_ches_ctx_bucket_count(const msm_ches_ctx *ctx) { return ctx ? CHES_DISPATCH(ctx, front().bucket_count()) : 0; }
+size_t msm_ches_ctx_bucket_count(const msm_ches_ctx *ctx) {
+  return ctx ? ctx->with([](auto &e) { return e.front().bucket_count(); }) : 0;
+}
 
-int msm_ches_ctx_batch_lanes(const msm_ches_ctx *ctx) { return ctx ? CHES_DISPATCH(ctx, front().batch_lanes()) : 0; }
+int msm_ches_ctx_batch_lanes(const msm_ches_ctx *ctx) {
+  return ctx ? ctx->with([](auto &e) { return e.front().batch_lanes(); }) : 0;
+}
 
 int msm_ches_ctx_time_accumulation(msm_ches_ctx *ctx, const byte *scalars, size_t set_stride, int nsets, int reps,
                                    float *ms) {
   if (!ctx || !scalars || !ms || nsets < 1 || reps < 1) return fail(MSM_E_ARG, "bad args");
   if (!ctx->ready) return fail(MSM_E_STATE, "no table");
-  if ((ctx->group == 1 ? ctx->g1->engines() : ctx->g2->engines()) != 1) return fail(MSM_E_ARG, "single-device contexts only");
-  try {
+  if (ctx->with([](auto &e) { return e.engines(); }) != 1) return fail(MSM_E_ARG, "single-device contexts only");
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
-    *ms = CHES_DISPATCH(ctx, front().time_accumulation((hipStream_t)0, scalars, set_stride, nsets, reps));
+    *ms = ctx->with([&](auto &e) {
+      return e.front().time_accumulation((hipStream_t)0, scalars, set_stride, nsets, reps);
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 void msm_ches_ctx_destroy(msm_ches_ctx *ctx) { delete ctx; }
 
 // ---------------- BGMW95 contexts ----------------
+// (a throwing Bgmw / Wbits constructor, and a throwing Wbits::get_table, give MSM_E_ARG
+// where the other families give MSM_E_HIP: kept as the callers have seen it)
 int msm_bgmw_ctx_create(msm_bgmw_ctx **ctx, int group, int device, int q_exp, int h) {
   if (!ctx || (group != 1 && group != 2)) return fail(MSM_E_ARG, "bad ctx/group");
-  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    auto c = std::make_unique<msm_bgmw_ctx>();
-    c->group = group;
-    c->device = device;
-    if (group == 1) c->g1 = std::make_unique<Bgmw<1>>(device, q_exp, h);
-    else c->g2 = std::make_unique<Bgmw<2>>(device, q_exp, h);
-    *ctx = c.release();
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_ARG, e.what());
-  }
+  if (!device_ok(device)) return no_device();
+  return create_ctx(ctx, group, device, MSM_E_ARG,
+                    [&](auto g) { return std::make_unique<Bgmw<decltype(g)::value>>(device, q_exp, h); });
 }
 
 int msm_bgmw_ctx_build_table(msm_bgmw_ctx *ctx, const void *pts, size_t n, int on_device, void *stream) {
   if (!ctx || (!pts && n)) return fail(MSM_E_ARG, "bad args");
-  try {
-    ctx->ready = false;
-    CHES_DISPATCH(ctx, build_table(pts, n, on_device != 0, (hipStream_t)stream));
-    ctx->ready = true;
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return set_table_ctx(ctx, [&](auto &e) { e.build_table(pts, n, on_device != 0, (hipStream_t)stream); });
 }
 
 int msm_bgmw_ctx_set_table(msm_bgmw_ctx *ctx, const void *tab, size_t n, int on_device, void *stream) {
   if (!ctx || (!tab && n)) return fail(MSM_E_ARG, "bad args");
-  try {
-    ctx->ready = false;
-    CHES_DISPATCH(ctx, set_table(tab, n, on_device != 0, (hipStream_t)stream));
-    ctx->ready = true;
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return set_table_ctx(ctx, [&](auto &e) { e.set_table(tab, n, on_device != 0, (hipStream_t)stream); });
 }
 
 int msm_bgmw_ctx_get_table(msm_bgmw_ctx *ctx, void *out, size_t first, size_t count) {
-  if (!ctx || (!out && count)) return fail(MSM_E_ARG, "bad args");
-  try {
-    CHES_DISPATCH(ctx, get_table(out, first, count, (hipStream_t)0));
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return get_table_ctx(ctx, out, first, count, MSM_E_HIP);
 }
 
 int msm_bgmw_ctx_mult(msm_bgmw_ctx *ctx, void *ret, const byte *scalars, size_t stride, int on_device,
                       void *stream) {
   if (!ctx || !ret || stride < 32) return fail(MSM_E_ARG, "bad args (stride must be >= 32)");
   if (!ctx->ready) return fail(MSM_E_STATE, "no table: build_table, set_table or load_table first");
-  try {
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    size_t n = CHES_DISPATCH(ctx, npoints());
-    const uint8_t *d = scalars;
-    if (!on_device && n) {
-      ctx->scalars.ensure(n * stride + 16);
-      MSM_HIP_CHECK(hipMemcpyAsync(ctx->scalars.p, scalars, n * stride, hipMemcpyHostToDevice, s));
-      d = ctx->scalars.as<uint8_t>();
-    }
-    if (ctx->group == 1) {
-      hfp::Jac<hfp::Fp> out;
-      ctx->g1->run(s, d, stride, &out);
-      memcpy(ret, &out, sizeof out);
-    } else {
-      hfp::Jac<hfp::Fp2> out;
-      ctx->g2->run(s, d, stride, &out);
-      memcpy(ret, &out, sizeof out);
-    }
+    ctx->with([&](auto &e) {
+      const uint8_t *d = stage_scalars(ctx->scalars, scalars, e.npoints() * stride, on_device != 0, s);
+      mult_out(e, ret, 1, [&](auto *out) { e.run(s, d, stride, out); });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 int msm_bgmw_ctx_set_profiling(msm_bgmw_ctx *ctx, int on) {
   if (!ctx) return fail(MSM_E_ARG, "null ctx");
-  CHES_DISPATCH(ctx, set_profiling(on != 0));
+  ctx->with([&](auto &e) { e.set_profiling(on != 0); });
   return MSM_OK;
 }
 
 int msm_bgmw_ctx_phase_times(const msm_bgmw_ctx *ctx, float out[6]) {
   if (!ctx || !out) return fail(MSM_E_ARG, "null");
-  const PhaseTimes &t = CHES_DISPATCH(ctx, times());
-  const float v[6] = {t.digits, t.sort, t.accumulate, t.reduce, t.finalize, t.total};
-  memcpy(out, v, sizeof v);
+  phase_times_out(ctx->with([](auto &e) -> const PhaseTimes & { return e.times(); }), out);
   return MSM_OK;
 }
 
-size_t msm_bgmw_ctx_bucket_count(const msm_bgmw_ctx *ctx) { return ctx ? CHES_DISPATCH(ctx, bucket_count()) : 0; }
+size_t msm_bgmw_ctx_bucket_count(const msm_bgmw_ctx *ctx) {
+  return ctx ? ctx->with([](auto &e) { return e.bucket_count(); }) : 0;
+}
 
 void msm_bgmw_ctx_destroy(msm_bgmw_ctx *ctx) { delete ctx; }
 
-int msm_ches_ctx_save_table(msm_ches_ctx *ctx, const char *path) {
-  if (!ctx || !path) return fail(MSM_E_ARG, "bad args");
-  try {
-    DeviceGuard g(ctx->device);
-    if (ctx->group == 1) {
-      const ChesParams &p = ctx->g1->params();
-      return save_table_file(*ctx->g1, 1, 1, p.q_exp, p.h, path);
-    }
-    const ChesParams &p = ctx->g2->params();
-    return save_table_file(*ctx->g2, 2, 1, p.q_exp, p.h, path);
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
-}
-int msm_ches_ctx_load_table(msm_ches_ctx *ctx, const char *path) {
-  if (!ctx || !path) return fail(MSM_E_ARG, "bad args");
-  try {
-    DeviceGuard g(ctx->device);
-    ctx->ready = false;
-    const ChesParams &p = CHES_DISPATCH(ctx, params());
-    const int rc = ctx->group == 1 ? load_table_file(*ctx->g1, 1, 1, p.q_exp, p.h, path)
-                                   : load_table_file(*ctx->g2, 2, 1, p.q_exp, p.h, path);
-    ctx->ready = rc == MSM_OK;
-    return rc;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
-}
-int msm_bgmw_ctx_save_table(msm_bgmw_ctx *ctx, const char *path) {
-  if (!ctx || !path) return fail(MSM_E_ARG, "bad args");
-  try {
-    DeviceGuard g(ctx->device);
-    if (ctx->group == 1) return save_table_file(*ctx->g1, 1, 2, ctx->g1->q_exp(), ctx->g1->h(), path);
-    return save_table_file(*ctx->g2, 2, 2, ctx->g2->q_exp(), ctx->g2->h(), path);
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
-}
-int msm_bgmw_ctx_load_table(msm_bgmw_ctx *ctx, const char *path) {
-  if (!ctx || !path) return fail(MSM_E_ARG, "bad args");
-  try {
-    DeviceGuard g(ctx->device);
-    ctx->ready = false;
-    const int rc = ctx->group == 1 ? load_table_file(*ctx->g1, 1, 2, ctx->g1->q_exp(), ctx->g1->h(), path)
-                                   : load_table_file(*ctx->g2, 2, 2, ctx->g2->q_exp(), ctx->g2->h(), path);
-    ctx->ready = rc == MSM_OK;
-    return rc;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
-}
+// ---------------- table files (method 1: CHES, 2: BGMW95) ----------------
+static const auto ches_qh = [](auto &e) { return std::make_pair(e.params().q_exp, e.params().h); };
+static const auto bgmw_qh = [](auto &e) { return std::make_pair(e.q_exp(), e.h()); };
+
+int msm_ches_ctx_save_table(msm_ches_ctx *ctx, const char *path) { return save_table_ctx(ctx, path, 1, ches_qh); }
+int msm_ches_ctx_load_table(msm_ches_ctx *ctx, const char *path) { return load_table_ctx(ctx, path, 1, ches_qh); }
+int msm_bgmw_ctx_save_table(msm_bgmw_ctx *ctx, const char *path) { return save_table_ctx(ctx, path, 2, bgmw_qh); }
+int msm_bgmw_ctx_load_table(msm_bgmw_ctx *ctx, const char *path) { return load_table_ctx(ctx, path, 2, bgmw_qh); }
 
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap) {
   if (q < 4 || a_h < 0) return 0;
@@ -1866,7 +1751,7 @@ size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap) {
 
 int msm_ches_digit_table(int q, int a_h, digit_decomposition *out) {
   if (q < 4 || a_h < 0 || !out) return fail(MSM_E_ARG, "bad args");
-  try {
+  return guarded(MSM_E_ARG, [&]() -> int {  // (MSM_E_ARG: host work only, what throws here is q / a_h)
     // decoded from the compact device tables (code + rank, ches_kernels.hpp)
     // with the device's arithmetic, so the golden digit-table hashes pin them
     std::vector<int> B = ches_bucket_set(q, a_h);
@@ -1887,9 +1772,7 @@ int msm_ches_digit_table(int q, int a_h, digit_decomposition *out) {
       out[d].alpha = (int)alpha;
     }
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_ARG, e.what());
-  }
+  });
 }
 
 // ---------------- boundary helpers ----------------
@@ -1955,110 +1838,61 @@ void msm_p2_add(blst_p2 *out, const blst_p2 *a, const blst_p2 *b) {
 }
 
 int msm_test_field(int group, int op, const limb_t *a, const limb_t *b, limb_t *out, size_t n) {
-  try {
-    if (group == 1) test_field<1>(op, a, b, out, n);
-    else test_field<2>(op, a, b, out, n);
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) { test_field<decltype(g)::value>(op, a, b, out, n); });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 int msm_test_xyzz(int group, const void *pts, size_t npts, const uint32_t *ops, int len, size_t nseq, void *out) {
-  try {
-    if (group == 1) test_xyzz<1>((const uint64_t *)pts, npts, ops, len, nseq, (uint64_t *)out);
-    else test_xyzz<2>((const uint64_t *)pts, npts, ops, len, nseq, (uint64_t *)out);
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      test_xyzz<decltype(g)::value>((const uint64_t *)pts, npts, ops, len, nseq, (uint64_t *)out);
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
 // ---------------- fixed-window (wbits) contexts ----------------
-#define WB_DISPATCH(ctx, CALL) ((ctx)->group == 1 ? (ctx)->g1->CALL : (ctx)->g2->CALL)
-
 int msm_wbits_ctx_create(msm_wbits_ctx **ctx, int group, int device, int wbits) {
   if (!ctx || (group != 1 && group != 2)) return fail(MSM_E_ARG, "bad ctx/group");
-  if (msm_device_count() <= device || device < 0) return fail(MSM_E_NODEV, "no such HIP device");
-  try {
-    auto c = std::make_unique<msm_wbits_ctx>();
-    c->group = group;
-    c->device = device;
-    if (group == 1) c->g1 = std::make_unique<Wbits<1>>(device, wbits);
-    else c->g2 = std::make_unique<Wbits<2>>(device, wbits);
-    *ctx = c.release();
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_ARG, e.what());
-  }
+  if (!device_ok(device)) return no_device();
+  return create_ctx(ctx, group, device, MSM_E_ARG,
+                    [&](auto g) { return std::make_unique<Wbits<decltype(g)::value>>(device, wbits); });
 }
 
 int msm_wbits_ctx_precompute(msm_wbits_ctx *ctx, const void *pts, size_t n, int on_device, void *stream) {
   if (!ctx || (!pts && n)) return fail(MSM_E_ARG, "bad args");
-  try {
-    ctx->ready = false;
-    WB_DISPATCH(ctx, precompute(pts, n, on_device != 0, (hipStream_t)stream));
-    ctx->ready = true;
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return set_table_ctx(ctx, [&](auto &e) { e.precompute(pts, n, on_device != 0, (hipStream_t)stream); });
 }
 
 int msm_wbits_ctx_set_table(msm_wbits_ctx *ctx, const void *tab, size_t n, int on_device, void *stream) {
   if (!ctx || (!tab && n)) return fail(MSM_E_ARG, "bad args");
-  try {
-    ctx->ready = false;
-    WB_DISPATCH(ctx, set_table(tab, n, on_device != 0, (hipStream_t)stream));
-    ctx->ready = true;
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  return set_table_ctx(ctx, [&](auto &e) { e.set_table(tab, n, on_device != 0, (hipStream_t)stream); });
 }
 
 int msm_wbits_ctx_get_table(msm_wbits_ctx *ctx, void *out, size_t first, size_t count) {
-  if (!ctx || (!out && count)) return fail(MSM_E_ARG, "bad args");
-  try {
-    WB_DISPATCH(ctx, get_table(out, first, count, (hipStream_t)0));
-    return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_ARG, e.what());
-  }
+  return get_table_ctx(ctx, out, first, count, MSM_E_ARG);
 }
 
 int msm_wbits_ctx_mult(msm_wbits_ctx *ctx, void *ret, const byte *scalars, size_t stride, size_t nbits,
                        int on_device, void *stream) {
   if (!ctx || !ret || stride == 0 || (nbits + 7) / 8 > stride) return fail(MSM_E_ARG, "bad args (stride < nbits/8)");
   if (!ctx->ready) return fail(MSM_E_STATE, "no table: precompute or set_table first");
-  try {
+  return guarded(MSM_E_HIP, [&] {
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const size_t n = WB_DISPATCH(ctx, npoints());
-    const uint8_t *d = scalars;
-    if (!on_device && n) {
-      ctx->scalars.ensure(n * stride + 16);
-      MSM_HIP_CHECK(hipMemcpyAsync(ctx->scalars.p, scalars, n * stride, hipMemcpyHostToDevice, s));
-      d = ctx->scalars.as<uint8_t>();
-    }
-    if (ctx->group == 1) {
-      hfp::Jac<hfp::Fp> out;
-      ctx->g1->run(s, d, stride, (int)nbits, &out);
-      memcpy(ret, &out, sizeof out);
-    } else {
-      hfp::Jac<hfp::Fp2> out;
-      ctx->g2->run(s, d, stride, (int)nbits, &out);
-      memcpy(ret, &out, sizeof out);
-    }
+    ctx->with([&](auto &e) {
+      const uint8_t *d = stage_scalars(ctx->scalars, scalars, e.npoints() * stride, on_device != 0, s);
+      mult_out(e, ret, 1, [&](auto *out) { e.run(s, d, stride, (int)nbits, out); });
+    });
     return MSM_OK;
-  } catch (const std::exception &e) {
-    return fail(MSM_E_HIP, e.what());
-  }
+  });
 }
 
-size_t msm_wbits_ctx_table_rows(const msm_wbits_ctx *ctx) { return ctx ? WB_DISPATCH(ctx, table_rows()) : 0; }
+size_t msm_wbits_ctx_table_rows(const msm_wbits_ctx *ctx) {
+  return ctx ? ctx->with([](auto &e) { return e.table_rows(); }) : 0;
+}
 
 void msm_wbits_ctx_destroy(msm_wbits_ctx *ctx) { delete ctx; }
-#undef WB_DISPATCH
 
 }  // extern "C"
-
