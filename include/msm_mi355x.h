@@ -760,6 +760,64 @@ int msm_sigs_reduce(int mode, const size_t *offsets, const size_t *pk_offsets, s
                     const uint8_t *sig_codes, const uint8_t *key_codes, const uint8_t *late, const uint8_t *is_one,
                     uint8_t *status);
 
+/* ---- bulk scalar-field arithmetic and batched NTTs (the loops over blst_fr_mul /
+ * blst_fr_add / blst_fr_sub a prover runs before it commits: ref src/exports.c
+ * blst_fr_*, bindings/blst.h:80-97) ----
+ * Elements are 32 bytes: blst_fr (four little-endian 64-bit limbs of a 2^256 mod r,
+ * canonical; the default) or blst_scalar (32 little-endian bytes of a).  A blst_fr
+ * source must be canonical and nothing is validated.
+ *
+ * msm_fr_ntt: `batch` transforms over consecutive arrays of n = 2^log_n elements,
+ * natural order in and out.  With omega = 7^((r - 1) / 2^32) and omega_n =
+ * omega^(2^(32 - log_n)):  forward dst[k] = sum_j src[j] omega_n^(j k);
+ * MSM_NTT_INVERSE dst[j] = n^-1 sum_k src[k] omega_n^(-j k).  shift: NULL or one HOST
+ * blst_scalar s, 0 < s < r: the forward transform first multiplies src[j] by s^j (it
+ * evaluates on the coset s <omega_n>), the inverse multiplies its result j by s^-j.
+ * MSM_FR_SRC_SCALAR / MSM_FR_DST_SCALAR select the blst_scalar form on either side,
+ * fused into the first load and the last store; a scalar-form source of any 256-bit
+ * value is taken mod r, as blst_fr_from_scalar takes it.  log_n = 0 is a copy, or a
+ * change of form.  dst == src is allowed (in place).
+ * batch == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: NULL dst or
+ * src with work to do, log_n above 26 (or batch 2^log_n above 2^40), unknown flag bits,
+ * a shift of 0 or >= r, a dst that overlaps src without being equal to it, device
+ * pointers not 8-byte aligned.  MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP failure;
+ * a host dst is then zero-filled.  Streams and thread safety as msm_points_to_affine
+ * (an engine pool keyed by device, counted by msm_engine_cache_stats(), freed by
+ * msm_release_engine_cache()).
+ * On the GPU: csrc/fr_ntt.hip.  Stockham passes planned by
+ * csrc/ntt_plan.hpp, each workgroup running its radix in LDS on a tile of 2^10 elements
+ * (MSM_NTT_TILE=<log2> in 2..11 overrides, read at each call); no pass only permutes.
+ * Chunks of whole transforms of at most 2^20 elements (MSM_NTT_CHUNK=<elements>
+ * overrides, read at each call; a longer transform is a chunk of its own); host memory
+ * goes through the pinned staging of the other bulk calls.
+ *
+ * msm_fr_op: dst[i] = a[i] op b[i], byte for byte what blst_fr_add / _sub / _mul / _sqr /
+ * blst_fr_cneg(.., 1) / blst_fr_inverse / blst_fr_from_scalar / blst_scalar_from_fr give.
+ * b is ignored by the one-operand ops; with MSM_FR_B_ONE it holds ONE element, used for
+ * every a[i].  a and b are on the side src_on_device names.  dst may equal a or b.
+ * MSM_FR_INV is one batch inversion per chunk, the product tree of msm_points_to_affine
+ * over Fr; the inverse of zero is zero (as blst_fr_inverse gives) and a zero disturbs
+ * no other element.  n == 0: MSM_OK.  MSM_E_ARG: an unknown op or flag bit, a NULL
+ * array that is read or written, a dst that overlaps a or b without being equal to it,
+ * misaligned device pointers.  Other errors, streams and the pool as msm_fr_ntt. */
+typedef struct { limb_t l[256 / 8 / sizeof(limb_t)]; } blst_fr; /* blst.h:57 */
+enum { MSM_NTT_INVERSE = 1, MSM_FR_SRC_SCALAR = 2, MSM_FR_DST_SCALAR = 4 };
+int msm_fr_ntt(int device, void *dst, const void *src, size_t log_n, size_t batch, const byte *shift, int flags,
+               int src_on_device, int dst_on_device, void *hip_stream);
+enum { MSM_FR_ADD, MSM_FR_SUB, MSM_FR_MUL, MSM_FR_SQR, MSM_FR_NEG, MSM_FR_INV, MSM_FR_FROM_SCALAR, MSM_FR_TO_SCALAR };
+enum { MSM_FR_B_ONE = 1 }; /* b holds ONE element, used for every a[i] */
+int msm_fr_op(int device, int op, void *dst, const void *a, const void *b, size_t n, int flags, int src_on_device,
+              int dst_on_device, void *hip_stream);
+/* host only, no device work.  msm_fr_root_of_unity: omega_n for n = 2^log_n, log_n <= 32,
+ * as a blst_fr.  msm_ntt_plan: the passes of a transform under the MSM_NTT_TILE set at
+ * the call: *npasses their number (0 for log_n = 0) and log_radix[i] the log2 of the
+ * radix of pass i (at most `capacity` written; may be NULL); log_n above 26: MSM_E_ARG. */
+int msm_fr_root_of_unity(size_t log_n, blst_fr *out);
+int msm_ntt_plan(size_t log_n, int *npasses, int log_radix[], int capacity);
+/* diagnostic: register-resident Fr products per second on `device` (out[0]) and the
+ * milliseconds the measurement took (out[1]) */
+int msm_fr_probe(int device, double out[2]);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

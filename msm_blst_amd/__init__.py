@@ -29,6 +29,9 @@ Mirrors:
   ps_verify, ps_aggregate_verify, ps_batch_verify,    blst_core_verify_pk_in_g{1,2} and the blst_pairing_chk_n_[mul_n_]aggr_pk_in_g{1,2}
   ps_in_group                                         / commit / finalverify sequences (ref aggregate.c), blst_p{1,2}_affine_in_g{1,2},
                                                       bulk, on the GPU
+  fr_ntt, fr_op, fr_root_of_unity, ntt_plan            batched NTTs over Fr and the loops over blst_fr_add / _sub / _mul /
+                                                      _sqr / _cneg / _inverse / _from_scalar / blst_scalar_from_fr (ref
+                                                      exports.c), bulk, on the GPU
 """
 import ctypes
 
@@ -44,6 +47,7 @@ __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext
            "ps_pairing", "ps_pairing_segments", "ps_pairing_check", "ps_final_exp", "fp12_one", "FP12_BYTES",
            "ps_verify", "ps_aggregate_verify", "ps_batch_verify", "ps_in_group", "sigs_plan", "sigs_reduce",
            "SIG_MIN_PK", "SIG_MIN_SIG",
+           "fr_ntt", "fr_op", "fr_root_of_unity", "ntt_plan", "fr_probe", "FR_OPS",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -57,6 +61,11 @@ PAIRING_MILLER_ONLY = 1                # MSM_PAIRING_MILLER_ONLY
 FP12_BYTES = 576                       # a GT value: blst_fp12
 SIG_MIN_PK, SIG_MIN_SIG = 1, 2         # MSM_SIG_*: the group of the public keys
 SIG_ENCODED = 2                        # MSM_SIG_ENCODED
+NTT_INVERSE, FR_SRC_SCALAR, FR_DST_SCALAR = 1, 2, 4  # MSM_NTT_INVERSE, MSM_FR_{SRC,DST}_SCALAR
+FR_B_ONE = 1                           # MSM_FR_B_ONE
+FR_BYTES = 32                          # a blst_fr or a blst_scalar
+# MSM_FR_*: the ops of fr_op, by name
+FR_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "neg": 4, "inv": 5, "from_scalar": 6, "to_scalar": 7}
 
 
 def device_count():
@@ -243,6 +252,103 @@ def ps_encode(group, points, n, *, compressed=True, jacobian=False, src_on_devic
     out = (ctypes.c_uint8 * (n * 48 * group * (1 if compressed else 2)))()
     check(lib().msm_points_encode(group, device, out, src, n, form, enc, 0, int(bool(src_on_device)), 0, stream))
     return bytes(out)
+
+
+def _fr_host(data, need, what):
+    src = _buf(data)
+    have = len(src) if hasattr(src, "__len__") else ctypes.sizeof(src)
+    if have < need:
+        raise ValueError(f"{have} bytes of {what} given, {need} needed")
+    return src
+
+
+def fr_ntt(data, log_n, batch=1, *, inverse=False, shift=None, src_scalar=False, dst_scalar=False,
+           src_on_device=False, dst=None, device=0, stream=None):
+    """`batch` transforms of 2^log_n Fr elements each (32 bytes: blst_fr, or blst_scalar
+    with src_scalar / dst_scalar) through msm_fr_ntt, natural order in and out:
+    forward dst[k] = sum_j src[j] omega_n^(j k), inverse dst[j] = n^-1 sum_k src[k]
+    omega_n^(-j k).  shift: None or s in (0, r), an int or 32 little-endian bytes; the
+    forward transform evaluates on the coset s <omega_n>, the inverse undoes it.  A
+    host source is a bytes-like object, a device source (src_on_device) a device
+    pointer.  Without dst the result comes back as bytes; with dst=<device pointer>
+    (which may be the source) it is written there, ordered on `stream`, and None is
+    returned."""
+    if not 0 <= log_n <= 26:
+        raise ValueError("log_n must be in [0, 26]")
+    if batch < 0:
+        raise ValueError("batch must be >= 0")
+    nbytes = (batch << log_n) * FR_BYTES
+    src = data if src_on_device else _fr_host(data, nbytes, "elements")
+    if shift is not None:
+        if isinstance(shift, int):
+            if not 0 < shift < (1 << 256):
+                raise ValueError("shift must be in (0, r)")
+            shift = shift.to_bytes(32, "little")
+        shift = _fr_host(shift, 32, "shift")
+    flags = (NTT_INVERSE if inverse else 0) | (FR_SRC_SCALAR if src_scalar else 0) | (FR_DST_SCALAR if dst_scalar else 0)
+    if dst is not None:
+        check(lib().msm_fr_ntt(device, dst, src, log_n, batch, shift, flags, int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * nbytes)()
+    check(lib().msm_fr_ntt(device, out, src, log_n, batch, shift, flags, int(bool(src_on_device)), 0, stream))
+    return bytes(out)
+
+
+def fr_op(op, a, b=None, n=None, *, b_one=False, src_on_device=False, dst=None, device=0, stream=None):
+    """dst[i] = a[i] op b[i] for i < n through msm_fr_op, byte for byte what the
+    reference's blst_fr_* give.  op: a name of FR_OPS ("add", "sub", "mul", "sqr",
+    "neg", "inv", "from_scalar", "to_scalar") or its number; b is read by add, sub and
+    mul only, and with b_one it holds ONE element used for every a[i].  The inverse
+    of zero is zero.  n defaults to the elements of a host `a`.  Host sources are
+    bytes-like objects, device sources (src_on_device, both) device pointers; with
+    dst=<device pointer> (which may be a or b) the result is written there, ordered on
+    `stream`, and None is returned."""
+    code = FR_OPS[op] if isinstance(op, str) else int(op)
+    two = code in (0, 1, 2)
+    if two and b is None:
+        raise ValueError("this op needs b")
+    if n is None:
+        if src_on_device:
+            raise ValueError("n must be given with device sources")
+        n = len(a) // FR_BYTES
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    if src_on_device:
+        pa, pb = a, b
+    else:
+        pa = _fr_host(a, n * FR_BYTES, "a")
+        pb = _fr_host(b, (min(n, 1) if b_one else n) * FR_BYTES, "b") if two else None
+    flags = FR_B_ONE if b_one else 0
+    if dst is not None:
+        check(lib().msm_fr_op(device, code, dst, pa, pb, n, flags, int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * (n * FR_BYTES))()
+    check(lib().msm_fr_op(device, code, out, pa, pb, n, flags, int(bool(src_on_device)), 0, stream))
+    return bytes(out)
+
+
+def fr_root_of_unity(log_n):
+    """omega_n for n = 2^log_n (log_n <= 32) as the 32 bytes of a blst_fr; omega_(2^32) =
+    7^((r - 1) / 2^32)."""
+    out = (ctypes.c_uint8 * FR_BYTES)()
+    check(lib().msm_fr_root_of_unity(log_n, out))
+    return bytes(out)
+
+
+def ntt_plan(log_n):
+    """log2 of the radix of every pass of a 2^log_n transform, under the MSM_NTT_TILE set
+    now (msm_ntt_plan; empty for log_n = 0)."""
+    n = ctypes.c_int(0)
+    radix = (ctypes.c_int * 32)()
+    check(lib().msm_ntt_plan(log_n, ctypes.byref(n), radix, 32))
+    return list(radix[:n.value])
+
+
+def fr_probe(device=0):
+    """(register-resident Fr products per second, milliseconds measured) on `device`."""
+    out = (ctypes.c_double * 2)()
+    check(lib().msm_fr_probe(device, out))
+    return out[0], out[1]
 
 
 def _segments(group, points, scalars, offsets, nbits, stride, src_on_device, dst, device, stream):

@@ -152,6 +152,11 @@ def lib():
     L.msm_sigs_chunk.restype = sz
     L.msm_sigs_plan.argtypes = [i32, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, sz]
     L.msm_sigs_reduce.argtypes = [i32, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.msm_fr_ntt.argtypes = [i32, vp, vp, sz, sz, vp, i32, i32, i32, vp]
+    L.msm_fr_op.argtypes = [i32, i32, vp, vp, vp, sz, i32, i32, i32, vp]
+    L.msm_fr_root_of_unity.argtypes = [sz, vp]
+    L.msm_ntt_plan.argtypes = [sz, vp, vp, i32]
+    L.msm_fr_probe.argtypes = [i32, vp]
     _lib = L
     return L
 

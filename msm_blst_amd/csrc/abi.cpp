@@ -23,7 +23,9 @@
 #include "decode.hpp"
 #include "encode.hpp"
 #include "engine.hpp"
+#include "fr_ntt.hpp"
 #include "hash_to_curve.hpp"
+#include "host_fr.hpp"
 #include "multi.hpp"
 #include "pairing.hpp"
 #include "point_segments.hpp"
@@ -1207,6 +1209,85 @@ int msm_points_to_affine(int group, int device, void *dst, const void *src, size
 }
 
 int msm_to_affine_levels(size_t npoints) { return (int)ta_levels(std::min(npoints, ta_chunk())).size(); }
+
+// ---- bulk Fr arithmetic and NTTs (csrc/fr_ntt.hip) ----
+int msm_fr_ntt(int device, void *dst, const void *src, size_t log_n, size_t batch, const byte *shift, int flags,
+               int src_on_device, int dst_on_device, void *hip_stream) {
+  const bool src_dev = src_on_device != 0, dst_dev = dst_on_device != 0;
+  if (log_n > (size_t)NTT_MAX_LOG) return fail(MSM_E_ARG, "log_n above 26");
+  if (flags & ~(MSM_NTT_INVERSE | MSM_FR_SRC_SCALAR | MSM_FR_DST_SCALAR)) return fail(MSM_E_ARG, "unknown flag bits");
+  if (batch == 0) return MSM_OK;  // nothing touched
+  if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
+  if (batch > (((size_t)1 << 40) >> log_n)) return fail(MSM_E_ARG, "batch out of range");
+  const size_t bytes = (batch << log_n) * 32;
+  if (shift) {
+    uint64_t w[4];
+    memcpy(w, shift, 32);  // (little-endian host, as the blst limbs everywhere here)
+    if (!(w[0] | w[1] | w[2] | w[3]) || hfr::geq_r(w)) return fail(MSM_E_ARG, "shift must be in (0, r)");
+  }
+  if (src_dev == dst_dev && dst != src && ranges_overlap(src, bytes, dst, bytes))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (src_dev && ((uintptr_t)src & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  if (!device_ok(device)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, bytes, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    bulk_run<FrNtt>(device, 0, src_dev, dst_dev, (hipStream_t)hip_stream, [&](FrNtt &e, hipStream_t cs) {
+      e.ntt(cs, src, dst, (int)log_n, batch, shift, flags, src_dev, dst_dev);
+    });
+    return MSM_OK;
+  }, on_throw);
+}
+
+int msm_fr_op(int device, int op, void *dst, const void *a, const void *b, size_t n, int flags, int src_on_device,
+              int dst_on_device, void *hip_stream) {
+  const bool src_dev = src_on_device != 0, dst_dev = dst_on_device != 0;
+  if (op < 0 || op >= FR_NOPS) return fail(MSM_E_ARG, "unknown op");
+  if (flags & ~MSM_FR_B_ONE) return fail(MSM_E_ARG, "unknown flag bits");
+  if (n == 0) return MSM_OK;
+  const bool two = fr_op_binary(op), b_one = (flags & MSM_FR_B_ONE) != 0;
+  if (!dst || !a || (two && !b)) return fail(MSM_E_ARG, "null dst / a / b");
+  if (n > ((size_t)1 << 40)) return fail(MSM_E_ARG, "n out of range");
+  const size_t bytes = n * 32, b_bytes = b_one ? 32 : bytes;
+  if (src_dev == dst_dev && ((dst != a && ranges_overlap(a, bytes, dst, bytes)) ||
+                             (two && !(dst == b && !b_one) && ranges_overlap(b, b_bytes, dst, bytes))))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (src_dev && ((((uintptr_t)a) | (two ? (uintptr_t)b : 0)) & 7) != 0)
+    return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  if (!device_ok(device)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, bytes, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    bulk_run<FrNtt>(device, 0, src_dev, dst_dev, (hipStream_t)hip_stream, [&](FrNtt &e, hipStream_t cs) {
+      e.op(cs, op, dst, a, two ? b : nullptr, n, b_one, src_dev, dst_dev);
+    });
+    return MSM_OK;
+  }, on_throw);
+}
+
+int msm_fr_root_of_unity(size_t log_n, blst_fr *out) {
+  if (log_n > 32 || !out) return fail(MSM_E_ARG, "log_n above 32 / null out");
+  const hfr::Fr w = hfr::root_of_unity((unsigned)log_n);
+  memcpy(out, &w, sizeof w);
+  return MSM_OK;
+}
+
+int msm_ntt_plan(size_t log_n, int *npasses, int log_radix[], int capacity) {
+  if (log_n > (size_t)NTT_MAX_LOG || !npasses) return fail(MSM_E_ARG, "log_n above 26 / null npasses");
+  const std::vector<int> plan = ntt_plan((int)log_n, ntt_tile());
+  *npasses = (int)plan.size();
+  for (int i = 0; log_radix && i < capacity && i < (int)plan.size(); ++i) log_radix[i] = plan[i];
+  return MSM_OK;
+}
+
+int msm_fr_probe(int device, double out[2]) {
+  if (!out) return fail(MSM_E_ARG, "null out");
+  if (!device_ok(device)) return no_device();
+  return guarded(MSM_E_HIP, [&] {
+    fr_probe(device, out);
+    return MSM_OK;
+  });
+}
 
 int msm_points_decode(int group, int device, void *dst, uint8_t *status, size_t *nbad, const void *src, size_t npoints,
                       int encoding, int flags, int src_on_device, int dst_on_device, void *hip_stream) {
