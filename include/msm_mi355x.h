@@ -631,7 +631,8 @@ int msm_h2c_dst_prime(byte *out, size_t *out_len, const byte *DST, size_t DST_le
  * is_one (nsegments bytes) and nfail are HOST memory and may be NULL: is_one[j] = 1 when
  * value j is one, *nfail = the number of values that are not; a call that passes either
  * returns only after they are written.  msm_fp12_final_exp: dst[i] = blst_final_exp of
- * the canonical non-zero value src[i] (a zero input is unspecified but completes).
+ * the canonical value src[i]; a zero input gives zero (verdict 0), as the reference's
+ * blst_final_exp does, and disturbs no other value.
  * p / q (one memory space), src and dst each in host or device memory (device pointers
  * 8-byte aligned), on HIP device `device`.
  * nsegments == 0 / n == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work:
@@ -845,6 +846,20 @@ int msm_test_field(int group, int op, const limb_t *a, const limb_t *b, limb_t *
  * two blst Jacobians: acc and acc+acc (via the xyzz+xyzz path) */
 int msm_test_xyzz(int group, const void *points_affine, size_t npoints, const uint32_t *ops, int len, size_t nseq,
                   void *out);
+/* one operation of the Fp12 tower (csrc/fp12l.hpp) on n values, one lane pair each, on
+ * device 0, synchronously.  op: 0 out = a b, 1 a^2, 2 a (x + y v + z v w) with x, y, z the
+ * coefficients 0, 1, 4 of b, 3 conj(a), 4 a^(p^k) (k = 1 .. 3), 5 1 / a, 6 a^(2^k) by k
+ * cyclotomic squarings held in registers (a unitary, k = 1 .. 64), 7 / 8 the doubling /
+ * addition step of the Miller loop with its line: a = (X, Y, Z, qx, qy, unused), out =
+ * (X3, Y3, Z3, l0, l1, l2).  alias: 0 a destination of its own, 1 the destination is a
+ * (ops 0 .. 4 and 6), 2 it is b (op 0).  raw 0: a, b, out are blst Fp12 values (576
+ * bytes; in through the arithmetic of msm_fp12_final_exp, out canonical); raw 1: the
+ * stored form, 672 bytes: six Fp2, each c0 | c1, 14 little-endian 28-bit limbs in
+ * uint32 of value 2^392 mod p, in and out untouched, so the caller chooses the
+ * representative (class S: limbs 0 .. 12 below 2^28, value below 2p) and sees the
+ * result's.  b is read by ops 0 and 2 only.  n == 0: MSM_OK.  MSM_E_ARG, before any
+ * device work: an unknown op, alias or raw, k out of range, a NULL array that is used. */
+int msm_test_fp12(int op, int k, int alias, int raw, const void *a, const void *b, void *out, size_t n);
 
 #ifdef __cplusplus
 }

@@ -648,7 +648,8 @@ def ps_pairing_check(p, q, offsets, *, src_on_device=False, device=0, stream=Non
 
 def ps_final_exp(f, n, *, src_on_device=False, dst=None, device=0, stream=None):
     """n final exponentiations (msm_fp12_final_exp): blst_final_exp of n canonical
-    non-zero blst_fp12 values.  Arguments as in ps_pairing."""
+    blst_fp12 values (a zero value gives zero, as the reference does).  Arguments as
+    in ps_pairing."""
     if n < 0:
         raise ValueError("n must be >= 0")
     if src_on_device:

@@ -1932,6 +1932,23 @@ int msm_test_xyzz(int group, const void *pts, size_t npts, const uint32_t *ops, 
     return MSM_OK;
   });
 }
+int msm_test_fp12(int op, int k, int alias, int raw, const void *a, const void *b, void *out, size_t n) {
+  if (op < TEST_FP12_MUL || op > TEST_FP12_LINE_ADD) return fail(MSM_E_ARG, "unknown op");
+  if (op == TEST_FP12_FROB && (k < 1 || k > 3)) return fail(MSM_E_ARG, "Frobenius power outside 1..3");
+  if (op == TEST_FP12_CSQR && (k < 1 || k > 64)) return fail(MSM_E_ARG, "squaring count outside 1..64");
+  const bool binary = op == TEST_FP12_MUL || op == TEST_FP12_SPARSE;
+  // d == a wherever the operation works from memory to memory and allows it; d == b for the product only
+  const bool alias_ok = alias == 0 || (alias == 1 && op <= TEST_FP12_CSQR && op != TEST_FP12_INV) ||
+                        (alias == 2 && op == TEST_FP12_MUL);
+  if (!alias_ok || (raw != 0 && raw != 1)) return fail(MSM_E_ARG, "bad alias / raw");
+  if (n && (!a || !out || (binary && !b))) return fail(MSM_E_ARG, "null operand");
+  if (!n) return MSM_OK;
+  if (!device_ok(0)) return no_device();
+  return guarded(MSM_E_HIP, [&] {
+    test_fp12(op, k, alias, raw != 0, a, binary ? b : nullptr, out, n);
+    return MSM_OK;
+  });
+}
 
 // ---------------- fixed-window (wbits) contexts ----------------
 int msm_wbits_ctx_create(msm_wbits_ctx **ctx, int group, int device, int wbits) {

@@ -18,6 +18,7 @@
 // k_reduce of kernels.hpp.
 #pragma once
 #include "bucket_sort.hpp"
+#include "fp2l_mem.hpp"
 #include "kernels.hpp"
 
 namespace msm {
@@ -27,36 +28,7 @@ namespace msm {
 constexpr uint32_t CH_IDX_MASK = 0x00ffffffu;
 
 // ---------------------------------------------------------------- inversion --
-// a^(p-2) mod p (Fermat), fixed 2-bit windows, input any lazy value, output S.
-// Inlined and register-lean (a, a^2, a^3 and the accumulator: ~60 VGPRs): the
-// earlier 4-bit version kept a 16-entry table in scratch (912 B/lane) and was
-// a call -- the table kernels that use it are now scratch-free.
-// One inversion per lane amortises over the lane's 3h table rows, so its ~570
-// products (vs ~490 with 4-bit windows) do not matter.
-__device__ constexpr uint64_t PM2[6] = {0xb9feffffffffaaa9ull, 0x1eabfffeb153ffffull, 0x6730d2a0f6b0f624ull,
-                                        0x64774b84f38512bfull, 0x4b1ba7b6434bacd7ull, 0x1a0111ea397fe69aull};
-__device__ __forceinline__ void fp_inv(Fp &r, const Fp &a) {
-  Fp a1 = a, a2, a3, acc;
-  fp_norm(a1);
-  fp_sqr(a2, a1);
-  fp_mul(a3, a2, a1);
-  fp_one(acc);
-  for (int k = 190; k >= 0; --k) {  // 2-bit windows of p - 2 (381 bits), from the top
-    if (k != 190) {
-      fp_sqr(acc, acc);
-      fp_sqr(acc, acc);
-    }
-    const uint32_t w = (uint32_t)(PM2[k >> 5] >> ((k & 31) * 2)) & 3u;  // uniform: the exponent is a constant
-    if (w) {
-      const uint32_t m1 = 0u - (uint32_t)(w == 1), m2 = 0u - (uint32_t)(w == 2), m3 = 0u - (uint32_t)(w == 3);
-      Fp t;
-#pragma unroll
-      for (int i = 0; i < NL; ++i) t.v[i] = (a1.v[i] & m1) | (a2.v[i] & m2) | (a3.v[i] & m3);
-      fp_mul(acc, acc, t);
-    }
-  }
-  r = acc;
-}
+// (fp_inv, the Fermat chain in Fp: fp2l_mem.hpp, shared with the host range-check build)
 __device__ __forceinline__ void f_inv(Fp &r, const Fp &a) { fp_inv(r, a); }
 // 1/(a0 + a1 i) = (a0 - a1 i) / (a0^2 + a1^2)
 __device__ __forceinline__ void f_inv(Fp2 &r, const Fp2 &a) {

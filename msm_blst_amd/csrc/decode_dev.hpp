@@ -131,7 +131,7 @@ __device__ __forceinline__ void dec_sel(Fp &r, bool c, const Fp &a) {  // r = c 
 }
 
 // a^((p-3)/4): fixed 2-bit windows of a constant exponent (uniform control
-// flow), as fp_inv (ches_kernels.hpp).  Input any lazy value, output S.
+// flow), as fp_inv (fp2l_mem.hpp).  Input any lazy value, output S.
 __device__ __forceinline__ void dec_pow_pm3d4(Fp &r, const Fp &a) {
   Fp a1 = a, a2, a3, acc;
   fp_norm(a1);

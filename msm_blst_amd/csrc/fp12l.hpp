@@ -1,4 +1,4 @@
-// fp12l.hpp -- the Fp6 / Fp12 tower of BLS12-381 on lane pairs (device only;
+// fp12l.hpp -- the Fp6 / Fp12 tower of BLS12-381 on lane pairs (device code;
 // replaces the reference's src/fp12_tower.c for the bulk pairings):
 //   Fp6 = Fp2[v] / (v^3 - xi),  Fp12 = Fp6[w] / (w^2 - v),  xi = 1 + u,
 // over the lane-pair Fp2L of fp2l.hpp: the even lane of a pair holds the real
@@ -15,9 +15,16 @@
 //
 // Ranges: every value between products is kept in class S;
 // t_add / t_sub reduce after each sum as h_add / h_sub of hash_to_curve.hip do,
-// so no lazy-range bookkeeping is needed and the proven bounds carry over.
+// so no lazy-range bookkeeping is needed and the proven bounds carry over: the
+// rows "Fp12 tower" of DESIGN.md 21 (tests/fp_bounds.py prove_tower) prove it,
+// and tests/host/fp12_host_shim.cpp runs this header's text on the host with
+// every range check armed (MSM_FP_HOST_TEST; tests/test_fp12_bounds.py).
 #pragma once
+#ifdef MSM_FP_HOST_TEST
+#include "fp2l_mem.hpp"
+#else
 #include "pair_kernels.hpp"
+#endif
 #include "pairing_consts.hpp"
 
 namespace msm {
@@ -46,7 +53,11 @@ MSM_FN void t_dbl(Fp2L &r, const Fp2L &a) { t_add(r, a, a); }
 // spend (one wave per SIMD) the scheduler otherwise interleaves the independent
 // products of a Karatsuba step and moves loads far ahead, and the kernels that
 // hold whole Fp12 values spill (tests/test_kernel_resources.py).
+#ifdef MSM_FP_HOST_TEST
+MSM_FN void t_fence() {}
+#else
 MSM_FN void t_fence() { __builtin_amdgcn_sched_barrier(0); }
+#endif
 MSM_FN void t_mul(Fp2L &r, const Fp2L &a, const Fp2L &b) {
   f_mul_bs(r, a, b);
   t_fence();
@@ -368,6 +379,89 @@ MSM_FN void t_cyc_sqr12(F12L &a) {
   t_cyc_hi(a.c[3], t21);
   t_cyc_hi(a.c[4], t01);
   t_cyc_hi(a.c[5], t11);
+}
+
+// ---------------------------------------------------------------- lines ----
+// The Miller loop's two steps (pairing.hip k_pair_miller): the Jacobian doubling
+// dbl-2009-alnr and the mixed addition madd-2007-bl with the lines of eprint
+// 2010/354, before the factors -2 x_P and 2 y_P.  T and Q in S; everything
+// that comes out is in S.
+// T = 2 T and the line through T: l0 = 6 X^3 - 4 Y^2, l1 = 3 X^2 Z^2, l2 = Z3 Z^2
+MSM_FN void pair_line_dbl(Fp2L &X, Fp2L &Y, Fp2L &Z, Fp2L &l0, Fp2L &l1, Fp2L &l2) {
+  Fp2L A, B, ZZ, C, D, E, F, X3, Z3, t;
+  t_sqr(A, X);
+  t_sqr(B, Y);
+  t_sqr(ZZ, Z);
+  t_sqr(C, B);
+  t_add(D, X, B);
+  t_sqr(D, D);
+  t_sub(D, D, A);
+  t_sub(D, D, C);
+  t_dbl(D, D);  // 2 ((X + B)^2 - A - C)
+  t_dbl(E, A);
+  t_add(E, E, A);  // 3 A
+  t_sqr(F, E);
+  t_sub(X3, F, D);
+  t_sub(X3, X3, D);
+  t_add(Z3, Y, Z);
+  t_sqr(Z3, Z3);
+  t_sub(Z3, Z3, B);
+  t_sub(Z3, Z3, ZZ);
+  t_add(l0, E, X);
+  t_sqr(l0, l0);
+  t_sub(l0, l0, A);
+  t_sub(l0, l0, F);
+  t_dbl(t, B);
+  t_dbl(t, t);
+  t_sub(l0, l0, t);
+  t_mul(l1, E, ZZ);
+  t_mul(l2, Z3, ZZ);
+  t_dbl(C, C);
+  t_dbl(C, C);
+  t_dbl(C, C);
+  t_sub(t, D, X3);
+  t_mul(t, t, E);
+  t_sub(Y, t, C);  // E (D - X3) - 8 C
+  X = X3;
+  Z = Z3;
+}
+// T = T + Q and the line through T and Q: l0 = 2 (r x_Q - y_Q Z3), l1 = r, l2 = Z3
+MSM_FN void pair_line_add(Fp2L &X, Fp2L &Y, Fp2L &Z, const Fp2L &qx, const Fp2L &qy, Fp2L &l0, Fp2L &l1,
+                          Fp2L &l2) {
+  Fp2L ZZ, U2, S2, H, HH, I, J, r, V, X3, Z3, t;
+  t_sqr(ZZ, Z);
+  t_mul(U2, qx, ZZ);
+  t_mul(S2, qy, Z);
+  t_mul(S2, S2, ZZ);
+  t_sub(H, U2, X);
+  t_sqr(HH, H);
+  t_dbl(I, HH);
+  t_dbl(I, I);
+  t_mul(J, H, I);
+  t_sub(r, S2, Y);
+  t_dbl(r, r);
+  t_mul(V, X, I);
+  t_sqr(X3, r);
+  t_sub(X3, X3, J);
+  t_sub(X3, X3, V);
+  t_sub(X3, X3, V);
+  t_add(Z3, Z, H);
+  t_sqr(Z3, Z3);
+  t_sub(Z3, Z3, ZZ);
+  t_sub(Z3, Z3, HH);
+  t_mul(J, J, Y);
+  t_sub(t, V, X3);
+  t_mul(t, t, r);
+  t_sub(t, t, J);
+  t_sub(Y, t, J);  // r (V - X3) - 2 Y J
+  t_mul(l0, r, qx);
+  t_mul(t, qy, Z3);
+  t_sub(l0, l0, t);
+  t_dbl(l0, l0);
+  l1 = r;
+  l2 = Z3;
+  X = X3;
+  Z = Z3;
 }
 
 }  // namespace msm

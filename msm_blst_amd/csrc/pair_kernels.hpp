@@ -5,25 +5,11 @@
 // several waves per SIMD instead of one).
 #pragma once
 #include "ches_kernels.hpp"
-#include "fp2l.hpp"
+#include "fp2l_mem.hpp"
 
 namespace msm {
 
-// component `comp` of an Fp2 stored at p (14 limbs, 8-B aligned: 56-B components)
-__device__ __forceinline__ void ld_comp(Fp &r, const Fp2 *p, int comp) {
-  const uint2 *s = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(p) + comp * sizeof(Fp));
-#pragma unroll
-  for (int i = 0; i < NL / 2; ++i) {
-    uint2 v = s[i];
-    r.v[2 * i] = v.x;
-    r.v[2 * i + 1] = v.y;
-  }
-}
-__device__ __forceinline__ void st_comp(Fp2 *p, const Fp &a, int comp) {
-  uint2 *d = reinterpret_cast<uint2 *>(reinterpret_cast<uint8_t *>(p) + comp * sizeof(Fp));
-#pragma unroll
-  for (int i = 0; i < NL / 2; ++i) d[i] = make_uint2(a.v[2 * i], a.v[2 * i + 1]);
-}
+// (ld_comp / st_comp, one component of a stored Fp2, and f_inv(Fp2L): fp2l_mem.hpp)
 template <class PT>
 __device__ __forceinline__ void ld_point2l(Aff<Fp2L> &r, const PT *p, int comp) {
   const Aff<Fp2> *q = reinterpret_cast<const Aff<Fp2> *>(p);
@@ -43,21 +29,6 @@ __device__ __forceinline__ void st_xyzz2l(Xyzz<Fp2> *p, const Xyzz<Fp2L> &a, int
   st_comp(&p->zz, a.zz.c, comp);
 }
 
-// 1 / (a0 + a1 i) = (a0 - a1 i) / (a0^2 + a1^2) on a lane pair: both lanes form
-// the norm a0^2 + a1^2 (own square + partner's square) and invert it (the same
-// instructions on both lanes), then scale their own (negated on odd lanes)
-// component.  a in S.
-__device__ __forceinline__ void f_inv(Fp2L &r, const Fp2L &a) {
-  Fp own = a.c, sq, psq, d, neg, x;
-  fp_norm(own);
-  fp_sqr(sq, own);
-  pair_swap(psq, sq);
-  fp_add(d, sq, psq);  // < 4p lazy
-  fp_inv(d, d);
-  fp_neg<4>(neg, own);
-  pair_sel(x, pair_odd(), neg, own);
-  fp_mul(r.c, x, d);
-}
 __device__ __forceinline__ void f_csub(Fp2L &a) { fp_csub_p(a.c); }
 
 // k_ches_table (ches_kernels.hpp) for G2 on lane pairs: lanes 2t, 2t + 1 build

@@ -100,83 +100,7 @@ static __global__ void __launch_bounds__(128)
   }
 }
 
-// T = 2 T and the line through T: l0 = 6 X^3 - 4 Y^2, l1 = 3 X^2 Z^2, l2 = Z3 Z^2
-__device__ __forceinline__ void pair_line_dbl(Fp2L &X, Fp2L &Y, Fp2L &Z, Fp2L &l0, Fp2L &l1, Fp2L &l2) {
-  Fp2L A, B, ZZ, C, D, E, F, X3, Z3, t;
-  t_sqr(A, X);
-  t_sqr(B, Y);
-  t_sqr(ZZ, Z);
-  t_sqr(C, B);
-  t_add(D, X, B);
-  t_sqr(D, D);
-  t_sub(D, D, A);
-  t_sub(D, D, C);
-  t_dbl(D, D);  // 2 ((X + B)^2 - A - C)
-  t_dbl(E, A);
-  t_add(E, E, A);  // 3 A
-  t_sqr(F, E);
-  t_sub(X3, F, D);
-  t_sub(X3, X3, D);
-  t_add(Z3, Y, Z);
-  t_sqr(Z3, Z3);
-  t_sub(Z3, Z3, B);
-  t_sub(Z3, Z3, ZZ);
-  t_add(l0, E, X);
-  t_sqr(l0, l0);
-  t_sub(l0, l0, A);
-  t_sub(l0, l0, F);
-  t_dbl(t, B);
-  t_dbl(t, t);
-  t_sub(l0, l0, t);
-  t_mul(l1, E, ZZ);
-  t_mul(l2, Z3, ZZ);
-  t_dbl(C, C);
-  t_dbl(C, C);
-  t_dbl(C, C);
-  t_sub(t, D, X3);
-  t_mul(t, t, E);
-  t_sub(Y, t, C);  // E (D - X3) - 8 C
-  X = X3;
-  Z = Z3;
-}
-// T = T + Q and the line through T and Q: l0 = 2 (r x_Q - y_Q Z3), l1 = r, l2 = Z3
-__device__ __forceinline__ void pair_line_add(Fp2L &X, Fp2L &Y, Fp2L &Z, const Fp2L &qx, const Fp2L &qy, Fp2L &l0,
-                                              Fp2L &l1, Fp2L &l2) {
-  Fp2L ZZ, U2, S2, H, HH, I, J, r, V, X3, Z3, t;
-  t_sqr(ZZ, Z);
-  t_mul(U2, qx, ZZ);
-  t_mul(S2, qy, Z);
-  t_mul(S2, S2, ZZ);
-  t_sub(H, U2, X);
-  t_sqr(HH, H);
-  t_dbl(I, HH);
-  t_dbl(I, I);
-  t_mul(J, H, I);
-  t_sub(r, S2, Y);
-  t_dbl(r, r);
-  t_mul(V, X, I);
-  t_sqr(X3, r);
-  t_sub(X3, X3, J);
-  t_sub(X3, X3, V);
-  t_sub(X3, X3, V);
-  t_add(Z3, Z, H);
-  t_sqr(Z3, Z3);
-  t_sub(Z3, Z3, ZZ);
-  t_sub(Z3, Z3, HH);
-  t_mul(J, J, Y);
-  t_sub(t, V, X3);
-  t_mul(t, t, r);
-  t_sub(t, t, J);
-  t_sub(Y, t, J);  // r (V - X3) - 2 Y J
-  t_mul(l0, r, qx);
-  t_mul(t, qy, Z3);
-  t_sub(l0, l0, t);
-  t_dbl(l0, l0);
-  l1 = r;
-  l2 = Z3;
-  X = X3;
-  Z = Z3;
-}
+// (pair_line_dbl / pair_line_add, the two line functions: fp12l.hpp)
 
 // lane pair t < npieces: out[t] = conj(prod over the pairs of piece t of the Miller function)
 static __global__ void __launch_bounds__(128)
@@ -564,6 +488,117 @@ void Pairing::run_final_exp(hipStream_t cs, const void *src, size_t n, void *dst
   }
   pend.flush();
   pipe_.finish(cs);
+}
+
+// ------------------------------------------------ per-operation test entry ----
+// msm_test_fp12 (include/msm_mi355x.h; tests/test_gpu_fp12_tower.py): one tower
+// operation per lane pair on stored values, with the lane mapping, the launch
+// bounds and the memory-to-memory forms of the kernels above.  The inversion has
+// a kernel of its own as k_pair_fe_inv has, and so have the two line functions,
+// which keep their point and line in registers.  The destination may be an
+// operand (the host passes the same pointer), hence no __restrict__.
+static __global__ void __launch_bounds__(128)
+    k_test_fp12(int op, int k, Fp12S *d, const Fp12S *a, const Fp12S *b, size_t n) {
+  PAIR_LANE();
+  if (t >= n) return;  // whole pairs only
+  switch (op) {
+    case TEST_FP12_MUL:
+      t_mul12(&d[t], &a[t], &b[t], comp);
+      break;
+    case TEST_FP12_SQR:
+      t_sqr12(&d[t], &a[t], comp);
+      break;
+    case TEST_FP12_SPARSE: {
+      Fp2L x, y, z;
+      ld_comp(x.c, &b[t].c[0], comp);
+      ld_comp(y.c, &b[t].c[1], comp);
+      ld_comp(z.c, &b[t].c[4], comp);
+      t_mul12_sparse(&d[t], &a[t], x, y, z, comp);
+      break;
+    }
+    case TEST_FP12_CONJ:
+      t_conj12(&d[t], &a[t], comp);
+      break;
+    case TEST_FP12_FROB:
+      t_frob12(&d[t], &a[t], k, comp);
+      break;
+    default: {  // TEST_FP12_CSQR: k squarings held in registers, as FE_CSQR
+      F12L v;
+      t_ld12(v, &a[t], comp);
+#pragma unroll 1
+      for (int i = 0; i < k; ++i) t_cyc_sqr12(v);
+      t_st12(&d[t], v, comp);
+      break;
+    }
+  }
+}
+static __global__ void __launch_bounds__(128) k_test_fp12_inv(Fp12S *d, const Fp12S *a, size_t n) {
+  PAIR_LANE();
+  if (t >= n) return;
+  t_inv12(&d[t], &a[t], comp);
+}
+// a[t]: X, Y, Z, qx, qy (the sixth slot is not read); d[t]: X3, Y3, Z3, l0, l1, l2
+static __global__ void __launch_bounds__(128) k_test_fp12_line(int add, Fp12S *d, const Fp12S *a, size_t n) {
+  PAIR_LANE();
+  if (t >= n) return;
+  Fp2L X, Y, Z, l0, l1, l2;
+  ld_comp(X.c, &a[t].c[0], comp);
+  ld_comp(Y.c, &a[t].c[1], comp);
+  ld_comp(Z.c, &a[t].c[2], comp);
+  if (add) {
+    Fp2L qx, qy;
+    ld_comp(qx.c, &a[t].c[3], comp);
+    ld_comp(qy.c, &a[t].c[4], comp);
+    pair_line_add(X, Y, Z, qx, qy, l0, l1, l2);
+  } else {
+    pair_line_dbl(X, Y, Z, l0, l1, l2);
+  }
+  st_comp(&d[t].c[0], X.c, comp);
+  st_comp(&d[t].c[1], Y.c, comp);
+  st_comp(&d[t].c[2], Z.c, comp);
+  st_comp(&d[t].c[3], l0.c, comp);
+  st_comp(&d[t].c[4], l1.c, comp);
+  st_comp(&d[t].c[5], l2.c, comp);
+}
+
+void test_fp12(int op, int k, int alias, bool raw, const void *a, const void *b, void *out, size_t n) {
+  if (!n) return;
+  DeviceGuard g(0);
+  constexpr size_t GT = Pairing::GT, S = Pairing::FP12S;
+  const dim3 grid(nblk(n * 2, 128)), block(128);
+  DevBuf da, db, dd, io;
+  da.ensure(n * S);
+  if (b) db.ensure(n * S);
+  if (!alias) dd.ensure(n * S);
+  if (!raw) io.ensure(n * GT);
+  auto up = [&](DevBuf &dst, const void *src) {
+    if (raw) {
+      MSM_HIP_CHECK(hipMemcpy(dst.p, src, n * S, hipMemcpyHostToDevice));
+    } else {  // the arithmetic of msm_fp12_final_exp's way in
+      MSM_HIP_CHECK(hipMemcpy(io.p, src, n * GT, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(k_pair_load, grid, block, 0, 0, (const uint64_t *)io.as<uint64_t>(), n, dst.as<Fp12S>());
+      MSM_HIP_CHECK(hipGetLastError());
+    }
+  };
+  up(da, a);
+  if (b) up(db, b);
+  Fp12S *A = da.as<Fp12S>(), *B = b ? db.as<Fp12S>() : nullptr;
+  Fp12S *D = alias == 1 ? A : alias == 2 ? B : dd.as<Fp12S>();
+  if (op == TEST_FP12_INV)
+    hipLaunchKernelGGL(k_test_fp12_inv, grid, block, 0, 0, D, (const Fp12S *)A, n);
+  else if (op == TEST_FP12_LINE_DBL || op == TEST_FP12_LINE_ADD)
+    hipLaunchKernelGGL(k_test_fp12_line, grid, block, 0, 0, op == TEST_FP12_LINE_ADD ? 1 : 0, D, (const Fp12S *)A, n);
+  else
+    hipLaunchKernelGGL(k_test_fp12, grid, block, 0, 0, op, k, D, (const Fp12S *)A, (const Fp12S *)B, n);
+  MSM_HIP_CHECK(hipGetLastError());
+  if (raw) {
+    MSM_HIP_CHECK(hipMemcpy(out, D, n * S, hipMemcpyDeviceToHost));
+  } else {  // its way out: the tail of k_pair_final_exp (an empty program)
+    hipLaunchKernelGGL(k_pair_final_exp, grid, block, 0, 0, (const Fp12S *)D, n, (Fp12S *)nullptr, io.as<uint64_t>(),
+                       (uint8_t *)nullptr, 0);
+    MSM_HIP_CHECK(hipGetLastError());
+    MSM_HIP_CHECK(hipMemcpy(out, io.p, n * GT, hipMemcpyDeviceToHost));
+  }
 }
 
 }  // namespace msm

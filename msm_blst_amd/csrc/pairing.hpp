@@ -81,4 +81,21 @@ class Pairing {
   void finish_kernels(hipStream_t s, size_t n, void *d_dst, uint8_t *d_st, bool final_exp);
 };
 
+// One tower operation on n values, device 0, synchronous (msm_test_fp12 of the C
+// ABI, which checks the arguments; test entry, not on any product path).  raw:
+// the 672-byte stored form in and out, else blst Fp12 values.  alias 1 / 2: the
+// destination is operand a / b.
+enum {
+  TEST_FP12_MUL = 0,
+  TEST_FP12_SQR = 1,
+  TEST_FP12_SPARSE = 2,
+  TEST_FP12_CONJ = 3,
+  TEST_FP12_FROB = 4,
+  TEST_FP12_INV = 5,
+  TEST_FP12_CSQR = 6,
+  TEST_FP12_LINE_DBL = 7,
+  TEST_FP12_LINE_ADD = 8
+};
+void test_fp12(int op, int k, int alias, bool raw, const void *a, const void *b, void *out, size_t n);
+
 }  // namespace msm

@@ -385,6 +385,259 @@ def trace_coop_add(group):
     return X3, Y3, zzz3, zz3
 
 
+# ------------------------------------------------- the Fp12 tower (fp12l.hpp) --
+# One Iv bounds both components of an Fp2 value (both lanes of a pair), as above.
+# Every t_* below mirrors the function of that name in fp12l.hpp; a product
+# demands class S of both operands (the header's claim: "every value between
+# products is kept in class S"), so a trace that completes has proven it for
+# the sequence it walks.
+def _need_S(x, what):
+    need(x.is_S(), f"{what}: operand not in class S: {x}")
+    return x
+
+
+def _w(x):
+    """a class-S bound widened to the class maximum (sound: every bound is an upper
+    bound), so the traces meet one operand bound per class and fp_red's exhaustive
+    check runs once per shape"""
+    return S() if x.is_S() else x
+
+
+def t_add(a, b):
+    return nred(add(_w(a), _w(b)))
+
+
+def t_sub(a, b):
+    return nred(sub(_w(a), _w(b), 4))     # f_sub4 wants b normalized and <= 4p: checked by sub()
+
+
+def t_dbl(a):
+    return t_add(a, a)
+
+
+def t_neg(a):
+    return nred(neg(_w(a), 4))
+
+
+def t_conj(a):
+    a = _w(a)
+    return union(nred(a), nred(neg(a, 4)))  # fp_cneg4: the even lane keeps a, the odd lane 4p - a
+
+
+def t_xi(a):
+    a = _w(a)
+    s = add(a, a)                         # odd lane: a1 + a0
+    d = sub(a, a, 4)                      # even lane: a0 + 4p - a1
+    return union(nred(s), nred(d))
+
+
+def t_mul(a, b):
+    _need_S(a, "t_mul a")
+    _need_S(b, "t_mul b")
+    return mul_bs_fp2(_w(a), _w(b))       # f_mul_bs(Fp2L): the two sums of f_mul_bs(Fp2), one per lane
+
+
+def t_sqr(a):
+    return sqr_fp2l(_w(_need_S(a, "t_sqr")))
+
+
+def t_scale(a, k):
+    return mul(_need_S(a, "t_scale a"), _need_S(k, "t_scale k"))
+
+
+def fp_inv_iv(a):
+    """fp_inv (fp2l_mem.hpp): any lazy input, normalized here; the 2-bit window chain"""
+    a1 = norm(a)
+    a2 = sqr(a1)
+    a3 = mul(a2, a1)
+    acc = S()                             # ONE28 and every later accumulator: checked to be a fixed point
+    for _ in range(2):
+        acc = sqr(acc)
+        need(acc.is_S(), "fp_inv: squared accumulator not S")
+    acc = mul(acc, union(a1, a2, a3))
+    need(acc.is_S(), "fp_inv: accumulator not S")
+    return acc
+
+
+def f_inv_fp2l(a):
+    """f_inv(Fp2L) (fp2l_mem.hpp): a in S; returns (norm, result)"""
+    own = norm(_need_S(a, "f_inv"))
+    sq = sqr(own)
+    d = add(sq, sq)                       # own square + the partner's
+    need(d.vmax < 4 * P, "f_inv: norm not below 4p")
+    inv = fp_inv_iv(d)
+    x = union(neg(own, 4), own)
+    return d, mul(x, inv)
+
+
+def pair_init_factors():
+    """k_pair_init (pairing.hip): -2 x_P and 2 y_P from canonical coordinates"""
+    x, y = canonical(), canonical()
+    px = nred(neg(nred(add(x, x)), 4))
+    py = nred(add(y, y))
+    return px, py
+
+
+def t_mulv6(a):
+    return [t_xi(a[2]), a[0], a[1]]
+
+
+def t_mul6(a, b):
+    t0, t1, t2 = t_mul(a[0], b[0]), t_mul(a[1], b[1]), t_mul(a[2], b[2])
+    m = t_mul(t_add(a[1], a[2]), t_add(b[1], b[2]))
+    m = t_xi(t_sub(t_sub(m, t1), t2))
+    r0 = t_add(m, t0)
+    m = t_mul(t_add(a[0], a[1]), t_add(b[0], b[1]))
+    m = t_sub(t_sub(m, t0), t1)
+    r1 = t_add(m, t_xi(t2))
+    m = t_mul(t_add(a[0], a[2]), t_add(b[0], b[2]))
+    m = t_sub(t_sub(m, t0), t2)
+    return [r0, r1, t_add(m, t1)]
+
+
+def t_mul6_xy0(a, x, y):
+    m0, m1 = t_mul(a[0], x), t_mul(a[1], y)
+    r0 = t_add(t_xi(t_mul(a[2], y)), m0)
+    m = t_mul(t_add(a[0], a[1]), t_add(x, y))
+    r1 = t_sub(t_sub(m, m0), m1)
+    return [r0, r1, t_add(t_mul(a[2], x), m1)]
+
+
+def t_mul6_0y0(a, z):
+    return [t_xi(t_mul(a[2], z)), t_mul(a[0], z), t_mul(a[1], z)]
+
+
+def t_cof6(a):
+    c0 = t_sub(t_sqr(a[0]), t_xi(t_mul(a[1], a[2])))
+    c1 = t_sub(t_xi(t_sqr(a[2])), t_mul(a[0], a[1]))
+    c2 = t_sub(t_sqr(a[1]), t_mul(a[0], a[2]))
+    t = t_xi(t_add(t_mul(c1, a[2]), t_mul(c2, a[1])))
+    return [c0, c1, c2], t_add(t, t_mul(c0, a[0]))
+
+
+def _add6(a, b):
+    return [t_add(x, y) for x, y in zip(a, b)]
+
+
+def _sub6(a, b):
+    return [t_sub(x, y) for x, y in zip(a, b)]
+
+
+def t_mul12(a, b):
+    t0, t1 = t_mul6(a[:3], b[:3]), t_mul6(a[3:], b[3:])
+    t2 = t_mul6(_add6(a[3:], a[:3]), _add6(b[3:], b[:3]))
+    t2 = _sub6(_sub6(t2, t0), t1)
+    return _add6(t0, t_mulv6(t1)) + t2
+
+
+def t_sqr12(a):
+    a0, a1 = a[:3], a[3:]
+    t0 = t_mul6(_add6(a0, a1), _add6(a0, t_mulv6(a1)))
+    t1 = t_mul6(a0, a1)
+    t0 = _sub6(_sub6(t0, t1), t_mulv6(t1))
+    return t0 + _add6(t1, t1)
+
+
+def t_mul12_sparse(a, x, y, z):
+    a0, a1 = a[:3], a[3:]
+    t0, t1 = t_mul6_xy0(a0, x, y), t_mul6_0y0(a1, z)
+    t2 = t_mul6_xy0(_add6(a0, a1), x, t_add(y, z))
+    t2 = _sub6(_sub6(t2, t0), t1)
+    return _add6(t0, t_mulv6(t1)) + t2
+
+
+def t_frob12(a, const):
+    return [t_mul(t_conj(c), const) for c in a]
+
+
+def t_inv12(a):
+    t0 = _sub6(t_mul6(a[:3], a[:3]), t_mulv6(t_mul6(a[3:], a[3:])))
+    cof, n = t_cof6(t0)
+    s = f_inv_fp2l(n)[1]
+    r = [t_mul(c, s) for c in cof]
+    return t_mul6(a[:3], r) + [t_neg(c) for c in t_mul6(a[3:], r)]
+
+
+def t_sqr4(a, b):
+    t0, t1 = t_sqr(a), t_sqr(b)
+    s = t_sqr(t_add(a, b))
+    r1 = t_sub(t_sub(s, t0), t1)
+    return t_add(t_xi(t1), t0), r1
+
+
+def t_cyc_lo(c, t):
+    return t_add(t_dbl(t_sub(t, c)), t)
+
+
+def t_cyc_hi(c, t):
+    return t_add(t_dbl(t_add(t, c)), t)
+
+
+def t_cyc_sqr12(a):
+    t00, t01 = t_sqr4(a[0], a[4])
+    t10, t11 = t_sqr4(a[3], a[2])
+    t20, t21 = t_sqr4(a[1], a[5])
+    return [t_cyc_lo(a[0], t00), t_cyc_lo(a[1], t10), t_cyc_lo(a[2], t20),
+            t_cyc_hi(a[3], t_xi(t21)), t_cyc_hi(a[4], t01), t_cyc_hi(a[5], t11)]
+
+
+def pair_line_dbl(X, Y, Z):
+    A, B, ZZ = t_sqr(X), t_sqr(Y), t_sqr(Z)
+    C = t_sqr(B)
+    D = t_dbl(t_sub(t_sub(t_sqr(t_add(X, B)), A), C))
+    E = t_add(t_dbl(A), A)
+    F = t_sqr(E)
+    X3 = t_sub(t_sub(F, D), D)
+    Z3 = t_sub(t_sub(t_sqr(t_add(Y, Z)), B), ZZ)
+    l0 = t_sub(t_sub(t_sub(t_sqr(t_add(E, X)), A), F), t_dbl(t_dbl(B)))
+    l1, l2 = t_mul(E, ZZ), t_mul(Z3, ZZ)
+    C8 = t_dbl(t_dbl(t_dbl(C)))
+    Y3 = t_sub(t_mul(t_sub(D, X3), E), C8)
+    return [X3, Y3, Z3, l0, l1, l2]
+
+
+def pair_line_add(X, Y, Z, qx, qy):
+    ZZ = t_sqr(Z)
+    U2 = t_mul(qx, ZZ)
+    S2 = t_mul(t_mul(qy, Z), ZZ)
+    H = t_sub(U2, X)
+    HH = t_sqr(H)
+    I = t_dbl(t_dbl(HH))
+    J = t_mul(H, I)
+    r = t_dbl(t_sub(S2, Y))
+    V = t_mul(X, I)
+    X3 = t_sub(t_sub(t_sub(t_sqr(r), J), V), V)
+    Z3 = t_sub(t_sub(t_sqr(t_add(Z, H)), ZZ), HH)
+    J = t_mul(J, Y)
+    Y3 = t_sub(t_sub(t_mul(t_sub(V, X3), r), J), J)
+    l0 = t_dbl(t_sub(t_mul(r, qx), t_mul(qy, Z3)))
+    return [X3, Y3, Z3, l0, r, Z3]
+
+
+def prove_tower():
+    """Every tower primitive and composite on class-S operands; returns {name: [outputs]}
+    (each output must be class S; a product fed anything else raises RangeError)."""
+    s = S()
+    six, twelve = [s] * 3, [s] * 6
+    res = {
+        "t_add": [t_add(s, s)], "t_sub": [t_sub(s, s)], "t_dbl": [t_dbl(s)], "t_neg": [t_neg(s)],
+        "t_conj": [t_conj(s)], "t_xi": [t_xi(s)],
+        "t_mul (f_mul_bs, S x S)": [t_mul(s, s)], "t_sqr (f_sqr, S)": [t_sqr(s)], "t_scale": [t_scale(s, s)],
+        "f_inv(Fp2L)": [f_inv_fp2l(s)[1]], "k_pair_init -2 x_P, 2 y_P": list(pair_init_factors()),
+        "t_mul6": t_mul6(six, six), "t_mul6_xy0": t_mul6_xy0(six, s, s), "t_mul6_0y0": t_mul6_0y0(six, s),
+        "t_cof6": (lambda c, n: c + [n])(*t_cof6(six)), "t_sqr4": list(t_sqr4(s, s)),
+        "t_cyc_lo / t_cyc_hi": [t_cyc_lo(s, s), t_cyc_hi(s, s)],
+        "t_mul12": t_mul12(twelve, twelve), "t_sqr12": t_sqr12(twelve),
+        "t_mul12_sparse": t_mul12_sparse(twelve, s, s, s), "t_frob12": t_frob12(twelve, canonical()),
+        "t_inv12": t_inv12(twelve), "t_cyc_sqr12": t_cyc_sqr12(twelve),
+        "pair_line_dbl": pair_line_dbl(s, s, s), "pair_line_add": pair_line_add(s, s, s, s, s),
+    }
+    for name, outs in res.items():
+        for o in outs:
+            need(o.is_S(), f"{name}: output not in class S: {o}")
+    return res
+
+
 def prove_all():
     """Run every trace; returns {name: [outputs]} (each output must be class S)."""
     res = {}
@@ -434,3 +687,6 @@ if __name__ == "__main__":
         print(f"{name:40s} " + "  ".join(f"{c}<{o.vmax / P:.4f}p" for c, o in zip("x y zzz zz".split(), outs)))
     for name, vin, vout in red_report():
         print(f"fp_red {name:36s} in < {vin:.3f}p -> out < {vout:.6f}p")
+    for name, outs in prove_tower().items():
+        print(f"tower {name:28s} {len(outs):2d} outputs, all S, largest < {max(o.vmax for o in outs) / P:.4f}p")
+    print(f"tower f_inv(Fp2L) norm sq + psq      < {f_inv_fp2l(S())[0].vmax / P:.4f}p (lazy, a legal fp_inv input)")

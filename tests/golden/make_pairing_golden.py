@@ -11,8 +11,14 @@ Writes tests/golden/pairing.json:
             ("ml") and its pairing ("e"): hex in full for the first 8, an FNV-1a 64
             of the 576 bytes for the rest; the pairs with infinity give one
   segments  per layout of pairing_inputs.SEGMENTS and segment: fe(prod ml), hex
+  tower     per special value of pairing_inputs.special_fp12(): the reference's
+            blst_fp12_mul, _sqr, _inverse, _conjugate, _frobenius_map (1 .. 3),
+            _mul_by_xy00z0 (the binary ones with "rand" as the second operand, the
+            sparse one with its coefficients 0, 1, 4), _cyclotomic_sqr of the value's
+            final exponentiation (FNV-1a 64 each) and blst_final_exp (hex); and that
+            the reference's final exponentiation of zero is zero
 While writing, the script asserts that the Python model agrees with the reference
-on every input point, every pairing and every segment.
+on every input point, every pairing, every segment and every tower entry.
 Test infrastructure only; data, no reference source text.
 """
 import ctypes
@@ -64,6 +70,39 @@ def ref_fe(L, f):
     return bytes(out)
 
 
+def ref_tower(L, a, b):
+    """the ten reference results on the Fp12 bytes a (second operand b), in the order of TOWER_OPS"""
+    def call(name, *args):
+        out = (ctypes.c_uint8 * 576)()
+        getattr(L, name)(out, *args)
+        return bytes(out)
+
+    conj = _buf(a)
+    L.blst_fp12_conjugate(conj)  # (in place)
+    xyz = b[0:192] + b[4 * 96:5 * 96]  # a blst_fp6 (x, y, z): coefficients 0, 1 and 4 of b
+    fe = call("blst_final_exp", _buf(a))
+    return [call("blst_fp12_mul", _buf(a), _buf(b)), call("blst_fp12_sqr", _buf(a)),
+            call("blst_fp12_inverse", _buf(a)), bytes(conj)] + [
+            call("blst_fp12_frobenius_map", _buf(a), ctypes.c_size_t(k)) for k in (1, 2, 3)] + [
+            call("blst_fp12_mul_by_xy00z0", _buf(a), _buf(xyz)), call("blst_fp12_cyclotomic_sqr", _buf(fe)), fe]
+
+
+def tower(L):
+    sp = pi.special_fp12()
+    b = sp["rand"]
+    out = {}
+    for name in pi.SPECIAL_NAMES:
+        ref = ref_tower(L, pi.fp12_bytes(sp[name]), pi.fp12_bytes(b))
+        model = pi.tower_model(sp[name], b)
+        for op, r, m in zip(pi.TOWER_OPS, ref, model):
+            assert r == pi.fp12_bytes(m), ("tower", name, op)
+        assert (L.blst_fp12_is_one(_buf(ref[-1])) == 1) == (name in pi.SPECIAL_FE_ONE), ("fe is one", name)
+        out[name] = {op: (r.hex() if op == "final_exp" else pi.fnv(r)) for op, r in zip(pi.TOWER_OPS, ref)}
+        print("tower", name, flush=True)
+    zero = ref_fe(L, bytes(576))
+    return {"values": out, "final_exp_of_zero_is_zero": zero == bytes(576)}
+
+
 def main():
     L = ctypes.CDLL(os.path.join(REPO, "oracle", "_ref", "libblst_ref.so"))
     L.blst_fp12_is_one.restype = ctypes.c_int
@@ -100,6 +139,8 @@ def main():
         segs[name] = res
         print(name, len(res), flush=True)
 
+    tw = tower(L)
+
     def ent(b, i):
         return b.hex() if i < FULL else pi.fnv(b)
 
@@ -107,9 +148,12 @@ def main():
         json.dump({"source": "reference libblst (oracle/_ref/libblst_ref.so) blst_miller_loop / blst_fp12_mul / "
                              "blst_final_exp on the inputs of tests/pairing_inputs.py (pairs(), SEGMENTS); ml = the "
                              "raw Miller value, e = the pairing, 576 bytes in blst's layout: hex for the first 8 "
-                             "pairs and every segment, FNV-1a 64 for the rest",
+                             "pairs and every segment, FNV-1a 64 for the rest; tower = blst_fp12_mul / _sqr / "
+                             "_inverse / _conjugate / _frobenius_map / _mul_by_xy00z0 / _cyclotomic_sqr (FNV-1a 64) "
+                             "and blst_final_exp (hex) on pairing_inputs.special_fp12(), second operand 'rand', "
+                             "cyclotomic_sqr taken on the value's final exponentiation",
                    "pairs": [{"ml": ent(ml[i], i), "e": ent(e[i], i)} for i in range(pi.N_PAIRS)],
-                   "segments": segs}, f, indent=0)
+                   "segments": segs, "tower": tw}, f, indent=0)
         f.write("\n")
 
 

@@ -320,3 +320,134 @@ SEGMENTS = {
     "inf_ends": [[INF_PAIRS[0], 3, 4, INF_PAIRS[1], 5, 6, INF_PAIRS[2]]],
     "inf_only": [list(INF_PAIRS)],
 }
+
+
+# ----------------------------------------- Fp12 values for the tower tests ----
+# (tests/test_fp12_bounds.py, tests/test_gpu_fp12_tower.py, tests/test_gpu_pairing.py,
+# tests/test_pairing_host.py and tests/golden/make_pairing_golden.py share them)
+SPECIAL_NAMES = ("one", "minus_one", "fp", "fp2", "fp6", "w_only", "w", "v", "line", "pm1", "half", "mont_max", "rand")
+# the final exponentiation of these is one, by its easy part (p^6 - 1)(p^2 + 1): a value
+# a0 in Fp6 has a0^(p^6) = a0, and a1 w with a1 in Fp6 has (a1 w)^(p^6 - 1) = -1, whose
+# p^2 + 1 power (an even one) is one
+SPECIAL_FE_ONE = ("one", "minus_one", "fp", "fp2", "fp6", "w_only", "w", "v")
+_SPECIAL = {}
+
+
+def random_fp12(n, seed):
+    import random
+    rnd = random.Random(seed)
+    return [[(rnd.randrange(P), rnd.randrange(P)) for _ in range(6)] for _ in range(n)]
+
+
+def special_fp12():
+    """{name: Fp12 value}, in the order of SPECIAL_NAMES (seeded)"""
+    if not _SPECIAL:
+        import random
+        rnd = random.Random(0xf12e)
+        f2 = lambda: (rnd.randrange(P), rnd.randrange(P))  # noqa: E731
+        z = F2_ZERO
+        mm = (P - 1) * ei.RINV % P  # the element whose blst Montgomery limbs are p - 1
+        v = {
+            "one": list(F12_ONE),
+            "minus_one": [(P - 1, 0)] + [z] * 5,
+            "fp": [(rnd.randrange(P), 0)] + [z] * 5,
+            "fp2": [f2()] + [z] * 5,
+            "fp6": [f2(), f2(), f2(), z, z, z],
+            "w_only": [z, z, z, f2(), f2(), f2()],
+            "w": [z, z, z, F2_ONE, z, z],
+            "v": [z, F2_ONE, z, z, z, z],
+            "line": [f2(), f2(), z, z, f2(), z],
+            "pm1": [(P - 1, P - 1)] * 6,
+            "half": [((P - 1) // 2, (P + 1) // 2)] * 6,
+            "mont_max": [(mm, mm)] * 6,
+            "rand": [f2() for _ in range(6)],
+        }
+        assert tuple(v) == SPECIAL_NAMES
+        _SPECIAL.update(v)
+    return _SPECIAL
+
+
+def special_list():
+    sp = special_fp12()
+    return [sp[k] for k in SPECIAL_NAMES]
+
+
+def unitary(f):
+    """an element of the cyclotomic subgroup: u = conj(f) / f, then u frob2(u)"""
+    u = f12_mul(f12_conj(f), f12_inv(f))
+    return f12_mul(u, f12_frob(u, 2))
+
+
+def f12_cyc_sqr(a, k=1):
+    for _ in range(k):
+        a = f12_sqr(a)
+    return a
+
+
+# the stored form of the engine (csrc/fp12l.hpp Fp12S): per coordinate value 2^392 mod p
+# in 14 little-endian 28-bit limbs (uint32); six Fp2, c0 | c1 each: 168 words, 672 bytes
+NL, R392 = 14, 1 << 392
+R392_INV = pow(R392, -1, P)
+FP12S_WORDS = 12 * NL
+
+
+def limbs28(v):
+    return [(v >> (28 * i)) & 0xfffffff for i in range(NL - 1)] + [v >> (28 * (NL - 1))]
+
+
+def stored_words(a, plus_p=False):
+    """Fp12 value -> 168 words: the canonical representative of every coordinate, or that plus p"""
+    out = []
+    for c in a:
+        for x in c:
+            out += limbs28(x * R392 % P + (P if plus_p else 0))
+    return out
+
+
+def stored_coords(words):
+    """168 words -> the twelve stored integers (not reduced)"""
+    assert len(words) == FP12S_WORDS
+    return [sum(int(w) << (28 * i) for i, w in enumerate(words[k * NL:(k + 1) * NL])) for k in range(12)]
+
+
+def stored_value(words):
+    """168 words -> the Fp12 value they hold"""
+    cs = [x * R392_INV % P for x in stored_coords(words)]
+    return [(cs[2 * j], cs[2 * j + 1]) for j in range(6)]
+
+
+def check_stored_S(words):
+    """class S: limbs 0 .. 12 below 2^28, every coordinate below 2p"""
+    for k in range(12):
+        assert all(w < (1 << 28) for w in words[k * NL:(k + 1) * NL - 1]), ("limb", k)
+    assert all(x < 2 * P for x in stored_coords(words)), "coordinate not below 2p"
+
+
+# the ten reference calls the fixture's "tower" key records per special value
+# (tests/golden/make_pairing_golden.py), and the model's value of each
+TOWER_OPS = ("mul", "sqr", "inverse", "conjugate", "frobenius1", "frobenius2", "frobenius3", "mul_by_xy00z0",
+             "cyclotomic_sqr", "final_exp")
+
+
+def tower_model(a, b):
+    """in the order of TOWER_OPS: binary ops with b, the sparse one with b's coefficients
+    0, 1, 4, the cyclotomic squaring on fe(a)"""
+    fe = final_exp(a)
+    return [f12_mul(a, b), f12_sqr(a), f12_inv(a), f12_conj(a), f12_frob(a, 1), f12_frob(a, 2), f12_frob(a, 3),
+            f12_mul_sparse(a, b[0], b[1], b[4]), f12_sqr(fe), fe]
+
+
+def miller_line_cases(pair_idx=(0, 1), steps=3):
+    """[(kind, T, Q)]: the running point at every line evaluation of the first `steps` steps
+    of miller_loop for the pairs pair_idx; the first of each pair is the doubling of T = Q, Z = 1"""
+    out = []
+    for i in pair_idx:
+        q = pairs()[i][1]
+        T = (q[0], q[1], F2_ONE)
+        for b in range(62, 62 - steps, -1):
+            out.append(("dbl", T, q))
+            T = line_dbl(T)[0]
+            if (Z_ABS >> b) & 1:
+                out.append(("add", T, q))
+                T = line_add(T, q)[0]
+    return out

@@ -258,3 +258,98 @@ def test_threads_and_engine_cache(m, fx):
     assert idle >= 1 and live >= idle and idle_bytes > 0  # the engines are back in the pool
     m.release_engine_cache()
     assert m.engine_cache_stats()[1] == 0
+
+
+# ---- the final exponentiation at its edges (msm_fp12_final_exp on arbitrary input) ----
+def special_bytes(names):
+    sp = pi.special_fp12()
+    return b"".join(pi.fp12_bytes(sp[k]) for k in names)
+
+
+def special_want(fx, names):
+    return bytes.fromhex("".join(fx["tower"]["values"][k]["final_exp"] for k in names))
+
+
+def fe_verdicts(m, src, n):
+    """(values, is_one bytes, nfail) of one msm_fp12_final_exp call on host memory"""
+    out = (ctypes.c_uint8 * (n * G))()
+    verdict = (ctypes.c_uint8 * n)(*([7] * n))
+    nfail = ctypes.c_size_t(99)
+    m.check(m.lib().msm_fp12_final_exp(0, out, verdict, ctypes.byref(nfail), src, n, 0, 0, None))
+    return bytes(out), bytes(verdict), nfail.value
+
+
+def test_final_exp_special_values_and_verdicts(m, fx):
+    """subfield elements, roots of one, the sparse shape of a line, all-maximal coordinates:
+    values byte for byte the reference's, and the verdict path on values that are exactly
+    one for another reason than an empty or cancelling segment"""
+    names = pi.SPECIAL_NAMES
+    src, want = special_bytes(names), special_want(fx, names)
+    got = m.ps_final_exp(src, len(names))
+    bad = [names[i] for i in range(len(names)) if vals(got)[i] != vals(want)[i]]
+    assert not bad, f"final exponentiation differs from the reference on {bad}"
+    ones = bytes(1 if v == pi.fp12_one() else 0 for v in vals(want))
+    assert ones == bytes(1 if k in pi.SPECIAL_FE_ONE else 0 for k in names) and sum(ones) == 8
+    out, verdict, nfail = fe_verdicts(m, src, len(names))
+    assert out == want and verdict == ones and nfail == len(names) - sum(ones)
+    # the verdicts alone (no values wanted)
+    verdict = (ctypes.c_uint8 * len(names))()
+    m.check(m.lib().msm_fp12_final_exp(0, None, verdict, None, src, len(names), 0, 0, None))
+    assert bytes(verdict) == ones
+
+
+def test_final_exp_zero_among_its_neighbours(m, fx):
+    """the all-zero value at slots 0, 31 and 64 of 65: the call returns MSM_OK, every other
+    slot is right, and the zero slots give zero, not one, as the reference's blst_final_exp
+    does (straight-line arithmetic: the Fermat chain of a zero norm is zero)"""
+    assert fx["tower"]["final_exp_of_zero_is_zero"] is True
+    n, zeros = 65, (0, 31, 64)
+    names = [pi.SPECIAL_NAMES[i % 13] for i in range(n)]
+    rnd = pi.random_fp12(8, 0xfe0)
+    src, want = [], []
+    for i in range(n):
+        if i in zeros:
+            src.append(bytes(G))
+            want.append(bytes(G))
+        elif i % 8 == 5:
+            src.append(pi.fp12_bytes(rnd[i // 8]))
+            want.append(pi.fp12_bytes(pi.final_exp(rnd[i // 8])))
+        else:
+            src.append(special_bytes([names[i]]))
+            want.append(special_want(fx, [names[i]]))
+    out, verdict, nfail = fe_verdicts(m, b"".join(src), n)
+    got = vals(out)
+    bad = [i for i in range(n) if i not in zeros and got[i] != want[i]]
+    assert not bad, f"non-zero slots {bad} differ beside a zero input"
+    assert [got[i] == bytes(G) for i in zeros] == [True] * 3, "fe(0) is not zero"
+    ones = bytes(1 if w == pi.fp12_one() else 0 for w in want)
+    assert verdict == ones and nfail == n - sum(ones) and all(verdict[i] == 0 for i in zeros)
+
+
+@pytest.mark.parametrize("chunk", [None, "64"])
+def test_final_exp_special_values_at_sizes(m, fx, monkeypatch, chunk):
+    if chunk:
+        monkeypatch.setenv("MSM_PAIRING_CHUNK", chunk)  # 65 and 129 cross chunk boundaries
+    for n in [1, 63, 64, 65, 129]:
+        names = [pi.SPECIAL_NAMES[(i + n) % 13] for i in range(n)]
+        want = special_want(fx, names)
+        out, verdict, nfail = fe_verdicts(m, special_bytes(names), n)
+        bad = [i for i in range(n) if vals(out)[i] != vals(want)[i]]
+        assert not bad, f"n={n} chunk={chunk}: slots {bad[:8]} differ"
+        ones = bytes(1 if k in pi.SPECIAL_FE_ONE else 0 for k in names)
+        assert verdict == ones and nfail == n - sum(ones), (n, chunk)
+
+
+def test_final_exp_special_values_in_device_memory(m, fx):
+    import torch
+    dev = torch.device("cuda:0")
+    names = pi.SPECIAL_NAMES
+    d_src = torch.frombuffer(bytearray(special_bytes(names)), dtype=torch.uint8).to(dev)
+    d_out = torch.zeros(len(names) * G, dtype=torch.uint8, device=dev)
+    st = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        assert m.ps_final_exp(d_src.data_ptr(), len(names), src_on_device=True, dst=d_out.data_ptr(),
+                              stream=st.cuda_stream) is None
+    st.synchronize()
+    assert bytes(d_out.cpu().numpy()) == special_want(fx, names)

@@ -44,7 +44,8 @@ def kernels():
 def test_every_kernel_found(kernels):
     names = " ".join(kernels)
     for k in ("k_accumulate", "k_accumulate2p", "k_segsum", "k_segsum2p", "k_ches_table", "k_ches_table2p",
-              "k_ches_front_hist", "k_finalize", "k_wbits_table2p", "k_wbits_sums2p", "k_test_xyzz2p"):
+              "k_ches_front_hist", "k_finalize", "k_wbits_table2p", "k_wbits_sums2p", "k_test_xyzz2p",
+              "k_test_fp12", "k_test_fp12_inv", "k_test_fp12_line"):
         assert k in names, k
 
 

@@ -66,6 +66,29 @@ def test_model_equals_fixture_segments(fx):
     assert fx["segments"]["inf_ends"][0] == pi.fp12_bytes(pi.pairing_product([ps[i] for i in (3, 4, 5, 6)])).hex()
 
 
+def test_model_equals_fixture_tower(fx):
+    """The ten reference calls per special value (blst_fp12_mul, _sqr, _inverse, _conjugate,
+    _frobenius_map 1 .. 3, _mul_by_xy00z0, _cyclotomic_sqr, blst_final_exp), recomputed with the
+    model: the oracle of the per-operation tower tests is pinned to the reference op by op."""
+    tw = fx["tower"]
+    sp = pi.special_fp12()
+    assert tuple(tw["values"]) == pi.SPECIAL_NAMES == tuple(sp) and len(sp) == 13
+    b = sp["rand"]
+    for name in pi.SPECIAL_NAMES:
+        want = tw["values"][name]
+        assert tuple(want) == pi.TOWER_OPS and len(pi.TOWER_OPS) == 10
+        for op, v in zip(pi.TOWER_OPS, pi.tower_model(sp[name], b)):
+            raw = pi.fp12_bytes(v)
+            assert (raw.hex() if op == "final_exp" else pi.fnv(raw)) == want[op], (name, op)
+        assert (want["final_exp"] == pi.fp12_one().hex()) == (name in pi.SPECIAL_FE_ONE), name
+    assert tw["final_exp_of_zero_is_zero"] is True
+    # the shapes the names promise
+    z = pi.F2_ZERO
+    assert sp["minus_one"] == [(pi.P - 1, 0)] + [z] * 5 and sp["w"][3] == pi.F2_ONE and sp["v"][1] == pi.F2_ONE
+    assert [j for j, c in enumerate(sp["line"]) if c != z] == [0, 1, 4]
+    assert pi.fp12_bytes(sp["mont_max"]) == (pi.P - 1).to_bytes(48, "little") * 12
+
+
 def test_model_is_bilinear():
     p, q = pi.pairs()[0]
     e = pi.pairing(p, q)
@@ -175,6 +198,31 @@ def test_argument_errors_before_any_device_work(m):
     assert L.msm_pairing_segments(-1, dst, None, None, None, None, empty, 2, 0, 0, 0, None) == MSM_E_NODEV
     assert L.msm_fp12_final_exp(-1, None, one, None, dst, 2, 0, 0, None) == MSM_E_NODEV
     assert bytes(dst) == bytes(len(dst)) and nf.value == 0  # nothing was touched
+
+
+def test_tower_test_entry_argument_errors(m):
+    """msm_test_fp12 (the per-operation entry of tests/test_gpu_fp12_tower.py): exported, declared,
+    and its argument checks come before any device work"""
+    L = m.lib()
+    with open(os.path.join(REPO, "include", "msm_mi355x.h")) as f:
+        assert "int msm_test_fp12(int op, int k, int alias, int raw, const void *a, const void *b, void *out, size_t n);" \
+            in f.read()
+    assert len(L.msm_test_fp12.argtypes) == 8
+    a = (ctypes.c_uint8 * 672)()
+    out = (ctypes.c_uint8 * 672)()
+    assert L.msm_test_fp12(0, 0, 0, 0, None, None, None, 0) == MSM_OK  # nothing to do
+    for op in (-1, 9, 100):
+        assert L.msm_test_fp12(op, 1, 0, 0, a, a, out, 1) == MSM_E_ARG, op  # unknown op
+    for k in (0, 4, -1):
+        assert L.msm_test_fp12(4, k, 0, 0, a, None, out, 1) == MSM_E_ARG, k  # Frobenius power outside 1..3
+    for k in (0, 65):
+        assert L.msm_test_fp12(6, k, 0, 0, a, None, out, 1) == MSM_E_ARG, k  # squaring count
+    assert L.msm_test_fp12(5, 0, 1, 0, a, None, out, 1) == MSM_E_ARG  # the inverse forbids d == a
+    assert L.msm_test_fp12(1, 0, 2, 0, a, a, out, 1) == MSM_E_ARG  # d == b for the product only
+    assert L.msm_test_fp12(0, 0, 3, 0, a, a, out, 1) == MSM_E_ARG and L.msm_test_fp12(0, 0, 0, 2, a, a, out, 1) == MSM_E_ARG
+    assert L.msm_test_fp12(0, 0, 0, 0, a, None, out, 1) == MSM_E_ARG  # the product reads b
+    assert L.msm_test_fp12(1, 0, 0, 0, None, None, out, 1) == MSM_E_ARG and L.msm_test_fp12(1, 0, 0, 0, a, None, None, 1) == MSM_E_ARG
+    assert bytes(out) == bytes(672)
 
 
 def test_wrapper_value_errors(m):
