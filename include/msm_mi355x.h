@@ -819,6 +819,98 @@ int msm_ntt_plan(size_t log_n, int *npasses, int log_radix[], int capacity);
  * milliseconds the measurement took (out[1]) */
 int msm_fr_probe(int device, double out[2]);
 
+/* ---- evaluation-form polynomials and KZG (what a blob proof or a PLONK opening is made
+ * of: evaluate outside the domain, divide by (X - z), commit the quotient, check it) ----
+ * msm_fr_eval_quotient.  polys: `count` consecutive arrays of n = 2^log_n blst_fr, the
+ * values of polynomial j (degree < n) on the domain of msm_fr_ntt, omega_n =
+ * msm_fr_root_of_unity(log_n): position i holds the value at x_i = omega_n^i, or with
+ * MSM_POLY_BITREV at omega_n^bitrev(i, log_n) (the order of EIP-4844 blobs).  z: count
+ * blst_fr, one point per polynomial (polys and z on the side src_on_device names).
+ * y[j] (count blst_fr, canonical) is the value of polynomial j at z[j].  q may be NULL;
+ * otherwise it receives count n elements, the values of (f_j - y_j) / (X - z_j) on the
+ * same domain in the same order, as blst_fr or, under MSM_FR_DST_SCALAR, as blst_scalar
+ * bytes (the form rides on the store; it is what an MSM reads).  y and q are on the
+ * side dst_on_device names; q == polys is allowed (in place).  Elements must be
+ * canonical and nothing is validated.
+ * With d_i = (z - x_i)^-1, the inverse of zero taken as zero (the MSM_FR_INV
+ * convention), S = sum f_i x_i d_i and T = sum x_i d_i:
+ *   z outside the domain:  y = (z^n - 1) n^-1 S,  q_i = (y - f_i) d_i
+ *   z = x_m:               y = f_m,  q_i = (y - f_i) d_i for i != m,  q_m = z^-1 (S - y T).
+ * count == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: NULL y, polys
+ * or z with work to do, log_n above 26 (or count 2^log_n above 2^40), unknown flag bits,
+ * a q that overlaps polys without being equal to it (or y / z overlapping another
+ * array), device pointers not 8-byte aligned.  MSM_E_NODEV: no such device.  MSM_E_HIP:
+ * a HIP failure; host y and q are then zero-filled.  Streams and thread safety as
+ * msm_points_to_affine (an engine pool keyed by device, counted by
+ * msm_engine_cache_stats(), freed by msm_release_engine_cache()).
+ * On the GPU: csrc/fr_poly.hip.  A workgroup inverts a tile of 2^10
+ * elements together (MSM_POLY_TILE=<log2> in 2..10 overrides, read at each call):
+ * prefix products per lane, a product tree over the lanes in LDS, one Fermat chain; the
+ * tiles of all polynomials of a chunk run side by side; a second kernel adds the
+ * partial sums of a polynomial's tiles and forms y, a third writes q.  Chunks of whole
+ * polynomials of at most 2^20 elements (MSM_POLY_CHUNK=<elements> overrides, read at
+ * each call; a longer polynomial is a chunk of its own); host memory goes through the
+ * pinned staging of the other bulk calls.
+ *
+ * msm_kzg_*: a context over one structured reference string in LAGRANGE form: n =
+ * 2^log_n G1 affine points L_i = [l_i(tau)]G1, l_i the Lagrange basis of the domain
+ * above, in natural order or, with MSM_POLY_BITREV in `flags` (fixed at creation), in
+ * bit-reversed order -- the order of the polynomials it is used with.  log_n <= 20.
+ * srs_lagrange_g1: host or device memory (srs_on_device), copied; tau_g2: one HOST
+ * blst_p2_affine, [tau]G2.  The context owns an msm_ctx (plain Pippenger) over the SRS.
+ *   commit: dst[j] = sum_i f_j[i] L_i = [f_j(tau)]G1, affine (all zero: infinity), for
+ *     `count` polynomials of n blst_fr.  The polynomials are turned into blst_scalar
+ *     bytes on the device (MSM_FR_TO_SCALAR) and summed by one msm_ctx_mult_batch per
+ *     chunk of MSM_POLY_CHUNK elements.
+ *   open: y[j] = f_j(z[j]) and proofs[j] = [q_j(tau)]G1 for q_j = (f_j - y_j) / (X - z_j):
+ *     msm_fr_eval_quotient under MSM_FR_DST_SCALAR into a device buffer, then the same
+ *     batch MSM; nothing of the quotient crosses to the host.  polys and z on the side
+ *     src_on_device names, proofs and y on the side dst_on_device names.
+ *   verify: `count` tuples (C_j, z_j, y_j, pi_j): commitments and proofs blst_p1_affine,
+ *     z and y blst_fr, all on the side src_on_device names.  weights == NULL: ok[j] = 1
+ *     iff e(C_j - [y_j]G1 + [z_j]pi_j, -G2) e(pi_j, [tau]G2) = 1 (G1, G2 the blst
+ *     generators): `count` verdicts; batch_offsets is ignored.  With weights (the
+ *     contract of msm_sigs_batch_verify: r_j the low nbits bits of the little-endian
+ *     string at weights + j weight_stride, nbits <= 256, taken mod r; weights is
+ *     always a HOST array), batch b covers
+ *     the tuples batch_offsets[b] .. batch_offsets[b + 1] (a HOST array of nbatches + 1
+ *     non-decreasing values, the last at most count; NULL: one batch of all tuples) and
+ *     ok[b] = 1 iff e(sum r_j (C_j - [y_j]G1 + [z_j]pi_j), -G2) e(sum r_j pi_j, [tau]G2)
+ *     = 1: one check of two pairs per batch; an empty batch gives 1.  The three scalars
+ *     of a tuple (r_j, -r_j y_j, r_j z_j) are computed on the HOST; the point sums run
+ *     through msm_points_msm_segments and the checks through msm_pairing_segments.  An
+ *     all-zero proof is infinity, a legal input (a constant polynomial opens to it).
+ *     Points are not validated: they must be on the curve and in the prime-order
+ *     subgroups (chain msm_points_decode / msm_points_in_group first).  ok (host, one
+ *     byte per verdict) and nfail (the number of zeros) may each be NULL, not both; the
+ *     call returns with them written.
+ * Every call is ordered on hip_stream; a call with a host destination returns with the
+ * data in place, one with a device destination after the batch MSM has finished (its
+ * Jacobians pass through the host, as msm_ctx_mult_batch returns them).  A context
+ * serves one call at a time.  count == 0: MSM_OK, nothing touched.  MSM_E_ARG, before
+ * any device work: a NULL context or array that is read or written, log_n above 20,
+ * unknown flag bits, misaligned device pointers, nbits > 256, a weight_stride shorter
+ * than (nbits + 7) / 8, a decreasing batch offset or one past count.  MSM_E_NODEV: no
+ * such device.  MSM_E_HIP: a HIP failure; host outputs are then zero-filled, ok filled
+ * with 0 and *nfail set to the number of verdicts.
+ * Out of scope: turning a monomial SRS into the Lagrange one, EIP-4844's Fiat-Shamir
+ * challenge and big-endian field bytes, multi-point openings, G2 commitments. */
+enum { MSM_POLY_BITREV = 8 }; /* shares the flag word with MSM_FR_DST_SCALAR (4) */
+int msm_fr_eval_quotient(int device, void *y, void *q, const void *polys, const void *z, size_t log_n, size_t count,
+                         int flags, int src_on_device, int dst_on_device, void *hip_stream);
+typedef struct msm_kzg_ctx msm_kzg_ctx;
+int msm_kzg_ctx_create(msm_kzg_ctx **ctx, int device, size_t log_n, const void *srs_lagrange_g1, int srs_on_device,
+                       const void *tau_g2, int flags, void *hip_stream);
+void msm_kzg_ctx_destroy(msm_kzg_ctx *ctx);
+int msm_kzg_commit(msm_kzg_ctx *ctx, void *dst_affine, const void *polys, size_t count, int src_on_device,
+                   int dst_on_device, void *hip_stream);
+int msm_kzg_open(msm_kzg_ctx *ctx, void *proofs_affine, void *y, const void *polys, const void *z, size_t count,
+                 int src_on_device, int dst_on_device, void *hip_stream);
+int msm_kzg_verify(msm_kzg_ctx *ctx, uint8_t *ok, size_t *nfail, const void *commitments, const void *z,
+                   const void *y, const void *proofs, size_t count, const byte *weights, size_t nbits,
+                   size_t weight_stride, const size_t *batch_offsets, size_t nbatches, int src_on_device,
+                   void *hip_stream);
+
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */
 size_t msm_ches_bucket_set(int q, int a_h, int *out, size_t cap);

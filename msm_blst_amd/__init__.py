@@ -32,6 +32,11 @@ Mirrors:
   fr_ntt, fr_op, fr_root_of_unity, ntt_plan            batched NTTs over Fr and the loops over blst_fr_add / _sub / _mul /
                                                       _sqr / _cneg / _inverse / _from_scalar / blst_scalar_from_fr (ref
                                                       exports.c), bulk, on the GPU
+  fr_eval_quotient                                    f(z) and (f - f(z)) / (X - z) of evaluation-form polynomials (no
+                                                      reference counterpart: the loop a KZG prover writes over blst_fr_*)
+  KZGContext                                          commit / open / verify over a Lagrange-form SRS: the chain of
+                                                      blst_p1s_mult_pippenger, blst_p1_mult and blst_miller_loop /
+                                                      blst_final_exp calls of a KZG prover and verifier, on the GPU
 """
 import ctypes
 
@@ -48,6 +53,7 @@ __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext
            "ps_verify", "ps_aggregate_verify", "ps_batch_verify", "ps_in_group", "sigs_plan", "sigs_reduce",
            "SIG_MIN_PK", "SIG_MIN_SIG",
            "fr_ntt", "fr_op", "fr_root_of_unity", "ntt_plan", "fr_probe", "FR_OPS",
+           "fr_eval_quotient", "KZGContext", "POLY_BITREV",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -63,6 +69,7 @@ SIG_MIN_PK, SIG_MIN_SIG = 1, 2         # MSM_SIG_*: the group of the public keys
 SIG_ENCODED = 2                        # MSM_SIG_ENCODED
 NTT_INVERSE, FR_SRC_SCALAR, FR_DST_SCALAR = 1, 2, 4  # MSM_NTT_INVERSE, MSM_FR_{SRC,DST}_SCALAR
 FR_B_ONE = 1                           # MSM_FR_B_ONE
+POLY_BITREV = 8                        # MSM_POLY_BITREV: positions in bit-reversed order
 FR_BYTES = 32                          # a blst_fr or a blst_scalar
 # MSM_FR_*: the ops of fr_op, by name
 FR_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "neg": 4, "inv": 5, "from_scalar": 6, "to_scalar": 7}
@@ -349,6 +356,137 @@ def fr_probe(device=0):
     out = (ctypes.c_double * 2)()
     check(lib().msm_fr_probe(device, out))
     return out[0], out[1]
+
+
+def fr_eval_quotient(polys, z, log_n, count=1, *, want_q=True, dst_scalar=False, bitrev=False, src_on_device=False,
+                     y_dst=None, q_dst=None, device=0, stream=None):
+    """`count` polynomials of 2^log_n blst_fr each, given by their values on the domain
+    of fr_ntt (position i: the value at omega_n^i, or with bitrev at omega_n^bitrev(i)),
+    and one blst_fr point z[j] per polynomial, through msm_fr_eval_quotient: y[j] = f_j(z[j])
+    and, with want_q, the values of (f_j - y_j) / (X - z_j) on the same domain in the
+    same order (blst_fr, or blst_scalar bytes with dst_scalar).  Host sources are
+    bytes-like objects, device sources (src_on_device, both) device pointers.  Returns
+    (y, q) as bytes (q None without want_q); with y_dst=<device pointer> (and q_dst,
+    which may be the source, when q is wanted) the results are written there, ordered
+    on `stream`, and None is returned."""
+    if not 0 <= log_n <= 26:
+        raise ValueError("log_n must be in [0, 26]")
+    if count < 0:
+        raise ValueError("count must be >= 0")
+    nbytes = (count << log_n) * FR_BYTES
+    if src_on_device:
+        pp, pz = polys, z
+    else:
+        pp, pz = _fr_host(polys, nbytes, "polynomial values"), _fr_host(z, count * FR_BYTES, "points")
+    flags = (FR_DST_SCALAR if dst_scalar else 0) | (POLY_BITREV if bitrev else 0)
+    sd = int(bool(src_on_device))
+    if y_dst is not None:
+        if want_q and q_dst is None:
+            raise ValueError("q_dst must be given with y_dst when the quotient is wanted")
+        check(lib().msm_fr_eval_quotient(device, y_dst, q_dst if want_q else None, pp, pz, log_n, count, flags, sd, 1,
+                                         stream))
+        return None
+    y = (ctypes.c_uint8 * max(count * FR_BYTES, 1))()
+    q = (ctypes.c_uint8 * max(nbytes, 1))() if want_q else None
+    check(lib().msm_fr_eval_quotient(device, y, q, pp, pz, log_n, count, flags, sd, 0, stream))
+    return bytes(y)[:count * FR_BYTES], (bytes(q)[:nbytes] if want_q else None)
+
+
+class KZGContext:
+    """KZG over one Lagrange-form SRS (msm_kzg_*): srs is 2^log_n blst_p1_affine points
+    L_i = [l_i(tau)]G1 in the order of the polynomials (natural, or bit-reversed with
+    bitrev), tau_g2 the 192 bytes of [tau]G2 (blst_p2_affine, host).  Polynomials are
+    2^log_n blst_fr values each; points and values blst_fr; commitments and proofs
+    blst_p1_affine (all zero: infinity)."""
+
+    def __init__(self, log_n, srs, tau_g2, *, bitrev=False, srs_on_device=False, device=0, stream=None):
+        if not 0 <= log_n <= 20:
+            raise ValueError("log_n must be in [0, 20]")
+        self.log_n, self.n, self.device, self.bitrev = log_n, 1 << log_n, device, bool(bitrev)
+        src = srs if srs_on_device else _fr_host(srs, self.n * POINT_BYTES[1], "SRS points")
+        tau = _fr_host(tau_g2, POINT_BYTES[2], "tau_g2")
+        self._h = ctypes.c_void_p()
+        check(lib().msm_kzg_ctx_create(ctypes.byref(self._h), device, log_n, src, int(bool(srs_on_device)), tau,
+                                       POLY_BITREV if bitrev else 0, stream))
+
+    def commit(self, polys, count=1, *, src_on_device=False, dst=None, stream=None):
+        """count commitments [f_j(tau)]G1 (bytes; with dst=<device pointer> written there, None returned)"""
+        src = polys if src_on_device else _fr_host(polys, count * self.n * FR_BYTES, "polynomial values")
+        if dst is not None:
+            check(lib().msm_kzg_commit(self._h, dst, src, count, int(bool(src_on_device)), 1, stream))
+            return None
+        out = (ctypes.c_uint8 * max(count * POINT_BYTES[1], 1))()
+        check(lib().msm_kzg_commit(self._h, out, src, count, int(bool(src_on_device)), 0, stream))
+        return bytes(out)[:count * POINT_BYTES[1]]
+
+    def open(self, polys, z, count=1, *, src_on_device=False, proofs_dst=None, y_dst=None, stream=None):
+        """(proofs, y): proofs[j] = [((f_j - y_j) / (X - z_j))(tau)]G1 and y[j] = f_j(z[j]); with
+        proofs_dst and y_dst (device pointers, both) written there and None returned"""
+        if src_on_device:
+            sp, sz_ = polys, z
+        else:
+            sp = _fr_host(polys, count * self.n * FR_BYTES, "polynomial values")
+            sz_ = _fr_host(z, count * FR_BYTES, "points")
+        if (proofs_dst is None) != (y_dst is None):
+            raise ValueError("proofs_dst and y_dst go together")
+        if proofs_dst is not None:
+            check(lib().msm_kzg_open(self._h, proofs_dst, y_dst, sp, sz_, count, int(bool(src_on_device)), 1, stream))
+            return None
+        pr = (ctypes.c_uint8 * max(count * POINT_BYTES[1], 1))()
+        y = (ctypes.c_uint8 * max(count * FR_BYTES, 1))()
+        check(lib().msm_kzg_open(self._h, pr, y, sp, sz_, count, int(bool(src_on_device)), 0, stream))
+        return bytes(pr)[:count * POINT_BYTES[1]], bytes(y)[:count * FR_BYTES]
+
+    def verify(self, commitments, z, y, proofs, count, *, weights=None, nbits=64, stride=None, batch_offsets=None,
+               src_on_device=False, stream=None):
+        """The verdict bytes (1: holds).  Without weights one per tuple (C_j, z_j, y_j, pi_j).
+        With weights (host bytes: count little-endian strings of `stride` >= (nbits + 7) / 8
+        bytes, the low nbits bits used) one per batch of batch_offsets (None: one batch of
+        all tuples): the weighted sums of the batch in one pairing check."""
+        if src_on_device:
+            pc, pz, py, ppi = commitments, z, y, proofs
+        else:
+            pc = _sig_points("commitments", commitments, count, POINT_BYTES[1], False)
+            ppi = _sig_points("proofs", proofs, count, POINT_BYTES[1], False)
+            pz = _sig_points("points", z, count, FR_BYTES, False)
+            py = _sig_points("values", y, count, FR_BYTES, False)
+        wb, bo, nb, nchk = None, None, 0, count
+        nbits = int(nbits)
+        if weights is not None:
+            if nbits < 0 or nbits > 256:
+                raise ValueError("nbits must be in 0 .. 256")
+            nby = (nbits + 7) // 8
+            stride = nby if stride is None else int(stride)
+            if stride < nby:
+                raise ValueError("stride shorter than (nbits + 7) / 8")
+            wb = _sig_points("weights", weights, 1, max((count - 1) * stride + nby, 0), False) if count else None
+            nchk = 1
+            if batch_offsets is not None:
+                offs = _check_offsets("batch_offsets", batch_offsets)
+                if offs[-1] > count:
+                    raise ValueError(f"batch_offsets ends at {offs[-1]} with {count} tuples")
+                bo, nb = (ctypes.c_size_t * len(offs))(*offs), len(offs) - 1
+                nchk = nb
+        if count == 0:
+            return b""
+        ok = (ctypes.c_uint8 * max(nchk, 1))()
+        nfail = ctypes.c_size_t(0)
+        check(lib().msm_kzg_verify(self._h, ok, ctypes.byref(nfail), pc, pz, py, ppi, count, wb, nbits, stride or 0, bo,
+                                   nb, int(bool(src_on_device)), stream))
+        out = bytes(ok[:nchk])
+        assert nfail.value == sum(1 for v in out if not v)
+        return out
+
+    def close(self):
+        if self._h:
+            lib().msm_kzg_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _segments(group, points, scalars, offsets, nbits, stride, src_on_device, dst, device, stream):

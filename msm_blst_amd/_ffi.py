@@ -158,6 +158,13 @@ def lib():
     L.msm_fr_root_of_unity.argtypes = [sz, vp]
     L.msm_ntt_plan.argtypes = [sz, vp, vp, i32]
     L.msm_fr_probe.argtypes = [i32, vp]
+    L.msm_fr_eval_quotient.argtypes = [i32, vp, vp, vp, vp, sz, sz, i32, i32, i32, vp]
+    L.msm_kzg_ctx_create.argtypes = [pp, i32, sz, vp, i32, vp, i32, vp]
+    L.msm_kzg_ctx_destroy.argtypes = [vp]
+    L.msm_kzg_ctx_destroy.restype = None
+    L.msm_kzg_commit.argtypes = [vp, vp, vp, sz, i32, i32, vp]
+    L.msm_kzg_open.argtypes = [vp, vp, vp, vp, vp, sz, i32, i32, vp]
+    L.msm_kzg_verify.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, vp]
     _lib = L
     return L
 

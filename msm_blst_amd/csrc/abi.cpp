@@ -24,8 +24,10 @@
 #include "encode.hpp"
 #include "engine.hpp"
 #include "fr_ntt.hpp"
+#include "fr_poly.hpp"
 #include "hash_to_curve.hpp"
 #include "host_fr.hpp"
+#include "kzg.hpp"
 #include "multi.hpp"
 #include "pairing.hpp"
 #include "point_segments.hpp"
@@ -849,6 +851,11 @@ struct msm_ctx : GroupCtx<Pippenger> {  // (`ready` unused: a context without po
   DevBuf decoded;  // msm_ctx_set_points_encoded: the decoded affine points
 };
 
+struct msm_kzg_ctx {
+  Kzg k;
+  msm_kzg_ctx(int device, int log_n, int flags, int window) : k(device, log_n, flags, window) {}
+};
+
 namespace {
 // ---------------- table file cache ----------------
 // file = 64-byte header + rows in blst affine layout (canonical Montgomery,
@@ -1265,6 +1272,38 @@ int msm_fr_op(int device, int op, void *dst, const void *a, const void *b, size_
   }, on_throw);
 }
 
+// ---- evaluation-form polynomials: value at a point and quotient (csrc/fr_poly.hip) ----
+int msm_fr_eval_quotient(int device, void *y, void *q, const void *polys, const void *z, size_t log_n, size_t count,
+                         int flags, int src_on_device, int dst_on_device, void *hip_stream) {
+  const bool src_dev = src_on_device != 0, dst_dev = dst_on_device != 0;
+  if (log_n > (size_t)POLY_MAX_LOG) return fail(MSM_E_ARG, "log_n above 26");
+  if (flags & ~(MSM_FR_DST_SCALAR | MSM_POLY_BITREV)) return fail(MSM_E_ARG, "unknown flag bits");
+  if (count == 0) return MSM_OK;  // nothing touched
+  if (!y || !polys || !z) return fail(MSM_E_ARG, "null y / polys / z");
+  if (count > (((size_t)1 << 40) >> log_n)) return fail(MSM_E_ARG, "count out of range");
+  const size_t bytes = (count << log_n) * 32, ybytes = count * 32;
+  if (q && src_dev == dst_dev && q != polys && ranges_overlap(polys, bytes, q, bytes))
+    return fail(MSM_E_ARG, "q overlaps polys without being equal to it");
+  if (src_dev == dst_dev && (ranges_overlap(polys, bytes, y, ybytes) || ranges_overlap(z, ybytes, y, ybytes) ||
+                             (q && (ranges_overlap(q, bytes, y, ybytes) || ranges_overlap(z, ybytes, q, bytes)))))
+    return fail(MSM_E_ARG, "y or z overlaps another array");
+  if (src_dev && ((((uintptr_t)polys) | ((uintptr_t)z)) & 7) != 0)
+    return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((((uintptr_t)y) | ((uintptr_t)q)) & 7) != 0)
+    return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  if (!device_ok(device)) return no_device();
+  const auto on_throw = [&] {
+    zero_host(y, ybytes, dst_dev);
+    zero_host(q, bytes, dst_dev);
+  };
+  return guarded(MSM_E_HIP, [&] {
+    bulk_run<FrPoly>(device, 0, src_dev, dst_dev, (hipStream_t)hip_stream, [&](FrPoly &e, hipStream_t cs) {
+      e.run(cs, polys, z, y, q, (int)log_n, count, flags, src_dev, dst_dev);
+    });
+    return MSM_OK;
+  }, on_throw);
+}
+
 int msm_fr_root_of_unity(size_t log_n, blst_fr *out) {
   if (log_n > 32 || !out) return fail(MSM_E_ARG, "log_n above 32 / null out");
   const hfr::Fr w = hfr::root_of_unity((unsigned)log_n);
@@ -1611,6 +1650,107 @@ int msm_ctx_phase_times(const msm_ctx *ctx, float out[6]) {
 }
 
 void msm_ctx_destroy(msm_ctx *ctx) { delete ctx; }
+
+// ---------------- KZG contexts (csrc/kzg.cpp) ----------------
+int msm_kzg_ctx_create(msm_kzg_ctx **ctx, int device, size_t log_n, const void *srs_lagrange_g1, int srs_on_device,
+                       const void *tau_g2, int flags, void *hip_stream) {
+  if (!ctx || !srs_lagrange_g1 || !tau_g2) return fail(MSM_E_ARG, "null ctx / srs / tau_g2");
+  if (log_n > (size_t)KZG_MAX_LOG) return fail(MSM_E_ARG, "log_n above 20");
+  if (flags & ~MSM_POLY_BITREV) return fail(MSM_E_ARG, "unknown flag bits");
+  if (srs_on_device && ((uintptr_t)srs_lagrange_g1 & 7) != 0) return fail(MSM_E_ARG, "device srs not 8-byte aligned");
+  if (!device_ok(device)) return no_device();
+  int rc = MSM_OK;
+  const int thrown = guarded(MSM_E_HIP, [&] {
+    auto c = std::make_unique<msm_kzg_ctx>(device, (int)log_n, flags, auto_window((size_t)1 << log_n));
+    rc = c->k.set_srs(srs_lagrange_g1, srs_on_device != 0, tau_g2, (hipStream_t)hip_stream);
+    if (rc == MSM_OK) *ctx = c.release();
+    return MSM_OK;
+  });
+  return thrown != MSM_OK ? thrown : rc;
+}
+
+void msm_kzg_ctx_destroy(msm_kzg_ctx *ctx) { delete ctx; }
+
+int msm_kzg_commit(msm_kzg_ctx *ctx, void *dst_affine, const void *polys, size_t count, int src_on_device,
+                   int dst_on_device, void *hip_stream) {
+  if (!ctx) return fail(MSM_E_ARG, "null ctx");
+  if (count == 0) return MSM_OK;  // nothing touched
+  if (!dst_affine || !polys) return fail(MSM_E_ARG, "null dst / polys");
+  if (count > (((size_t)1 << 40) >> ctx->k.log_n())) return fail(MSM_E_ARG, "count out of range");
+  const bool src_dev = src_on_device != 0, dst_dev = dst_on_device != 0;
+  if (src_dev && ((uintptr_t)polys & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst_affine & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const auto on_throw = [&] { zero_host(dst_affine, count * 96, dst_dev); };
+  int rc = MSM_OK;
+  const int thrown = guarded(MSM_E_HIP, [&] {
+    rc = ctx->k.commit(dst_affine, polys, count, src_dev, dst_dev, (hipStream_t)hip_stream);
+    return MSM_OK;
+  }, on_throw);
+  if (thrown == MSM_OK && rc != MSM_OK) on_throw();
+  return thrown != MSM_OK ? thrown : rc;
+}
+
+int msm_kzg_open(msm_kzg_ctx *ctx, void *proofs_affine, void *y, const void *polys, const void *z, size_t count,
+                 int src_on_device, int dst_on_device, void *hip_stream) {
+  if (!ctx) return fail(MSM_E_ARG, "null ctx");
+  if (count == 0) return MSM_OK;  // nothing touched
+  if (!proofs_affine || !y || !polys || !z) return fail(MSM_E_ARG, "null proofs / y / polys / z");
+  if (count > (((size_t)1 << 40) >> ctx->k.log_n())) return fail(MSM_E_ARG, "count out of range");
+  const bool src_dev = src_on_device != 0, dst_dev = dst_on_device != 0;
+  if (src_dev && ((((uintptr_t)polys) | ((uintptr_t)z)) & 7) != 0)
+    return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((((uintptr_t)proofs_affine) | ((uintptr_t)y)) & 7) != 0)
+    return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  const auto on_throw = [&] {
+    zero_host(proofs_affine, count * 96, dst_dev);
+    zero_host(y, count * 32, dst_dev);
+  };
+  int rc = MSM_OK;
+  const int thrown = guarded(MSM_E_HIP, [&] {
+    rc = ctx->k.open(proofs_affine, y, polys, z, count, src_dev, dst_dev, (hipStream_t)hip_stream);
+    return MSM_OK;
+  }, on_throw);
+  if (thrown == MSM_OK && rc != MSM_OK) on_throw();
+  return thrown != MSM_OK ? thrown : rc;
+}
+
+int msm_kzg_verify(msm_kzg_ctx *ctx, uint8_t *ok, size_t *nfail, const void *commitments, const void *z,
+                   const void *y, const void *proofs, size_t count, const byte *weights, size_t nbits,
+                   size_t weight_stride, const size_t *batch_offsets, size_t nbatches, int src_on_device,
+                   void *hip_stream) {
+  if (weights) {
+    if (nbits > 256) return fail(MSM_E_ARG, "nbits must be at most 256");
+    if (weight_stride < (nbits + 7) / 8) return fail(MSM_E_ARG, "weight_stride shorter than (nbits + 7) / 8");
+    if (weight_stride > ((size_t)1 << 20)) return fail(MSM_E_ARG, "weight_stride out of range");
+    if (batch_offsets) {
+      if (nbatches > ((size_t)1 << 32)) return fail(MSM_E_ARG, "nbatches out of range");
+      if (!seg_offsets_ok(batch_offsets, nbatches)) return fail(MSM_E_ARG, "batch offsets decrease");
+      if (batch_offsets[nbatches] > count) return fail(MSM_E_ARG, "batch offsets past the tuples");
+    }
+  }
+  if (!ctx) return fail(MSM_E_ARG, "null ctx");
+  if (count == 0) return MSM_OK;  // nothing touched
+  if (!ok && !nfail) return fail(MSM_E_ARG, "null ok and nfail");
+  if (!commitments || !z || !y || !proofs) return fail(MSM_E_ARG, "null commitments / z / y / proofs");
+  if (count > ((size_t)1 << 32)) return fail(MSM_E_ARG, "count out of range");
+  const bool src_dev = src_on_device != 0;
+  if (src_dev && ((((uintptr_t)commitments) | ((uintptr_t)z) | ((uintptr_t)y) | ((uintptr_t)proofs)) & 7) != 0)
+    return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  const size_t nchk = weights ? (batch_offsets ? nbatches : 1) : count;
+  if (nchk == 0) return MSM_OK;
+  const auto on_throw = [&] {
+    if (ok) memset(ok, 0, nchk);
+    if (nfail) *nfail = nchk;
+  };
+  int rc = MSM_OK;
+  const int thrown = guarded(MSM_E_HIP, [&] {
+    rc = ctx->k.verify(ok, nfail, commitments, z, y, proofs, count, weights, nbits, weight_stride, batch_offsets,
+                       nbatches, src_dev, (hipStream_t)hip_stream);
+    return MSM_OK;
+  }, on_throw);
+  if (thrown == MSM_OK && rc != MSM_OK) on_throw();
+  return thrown != MSM_OK ? thrown : rc;
+}
 
 // ---------------- CHES contexts ----------------
 static void params_out(const ChesParams &p, int out[9]) {

@@ -33,38 +33,12 @@
 #include <cstring>
 #include <type_traits>
 
-#include "fr.hpp"
-#include "host_fr.hpp"
+#include "fr_mem.hpp"
 #include "to_affine.hpp"
 
 namespace msm {
 
 namespace {
-
-struct FrK {  // an Fr as a kernel argument
-  uint32_t v[FR_NL];
-};
-
-// ---- at rest: 32 bytes, 8-byte aligned ----
-__device__ __forceinline__ void fr_ld(Fr &r, const uint32_t *p) {
-  const uint2 *s = reinterpret_cast<const uint2 *>(p);
-  uint32_t w[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint2 v = s[i];
-    w[2 * i] = v.x;
-    w[2 * i + 1] = v.y;
-  }
-  fr_unpack(r, w);
-}
-__device__ __forceinline__ void fr_st(uint32_t *p, const Fr &a) {
-  uint32_t w[8];
-  fr_pack(w, a);
-  uint2 *d = reinterpret_cast<uint2 *>(p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) d[i] = make_uint2(w[2 * i], w[2 * i + 1]);
-}
-__device__ __forceinline__ void fr_arg(Fr &r, const FrK &k) { fr_set(r, k.v); }
 
 // ---- LDS: planar with a skew ----
 __device__ __forceinline__ uint32_t lds_at(uint32_t e) { return e + (e >> 5); }
@@ -422,30 +396,16 @@ static __global__ void __launch_bounds__(256) k_fr_probe(uint32_t *out, int iter
 }
 
 // ---- host side ----
-// a 256-bit value as nine 29-bit limbs
-void limbs29(uint32_t out[FR_NL], const hfr::Fr &v) {
-  for (int i = 0; i < FR_NL; ++i) {
-    const int bit = FR_B * i, j = bit / 64, off = bit % 64;
-    uint64_t w = v.l[j] >> off;
-    if (off && j + 1 < 4) w |= v.l[j + 1] << (64 - off);
-    out[i] = (uint32_t)w & FR_MASK;
-  }
-}
-// the field element with blst_fr x, as the constant x 2^261 mod r the kernels multiply by
-FrK internal(const hfr::Fr &x) {
-  FrK k;
-  limbs29(k.v, hfr::mul(x, hfr::from_u64(32)));
-  return k;
-}
+FrK internal(const hfr::Fr &x) { return fr_internal(x); }
 const hfr::Fr kPlainOne = {{1, 0, 0, 0}};  // the blst_fr of 2^-256
 
-void pow_table(hipStream_t s, uint32_t *out, size_t count, const hfr::Fr &base, const hfr::Fr &mult) {
+}  // namespace
+
+void fr_pow_table(hipStream_t s, uint32_t *out, size_t count, const hfr::Fr &base, const hfr::Fr &mult) {
   hipLaunchKernelGGL(k_fr_pow_table, dim3(nblk(count, 256)), dim3(256), 0, s, out, (uint32_t)count, internal(base),
                      internal(mult));
   MSM_HIP_CHECK(hipGetLastError());
 }
-
-}  // namespace
 
 size_t FrNtt::device_bytes() const {
   size_t b = ta_.bytes + tb_.bytes + lv_.bytes + sh_.bytes + in_.device_bytes() + inb_.device_bytes() +
@@ -464,16 +424,16 @@ const FrNtt::Tables &FrNtt::tables(hipStream_t s, int log_n) {
   t.buf.ensure((n_lo + (n_hi > 1 ? n_hi : 0) + n_in) * EL);
   uint32_t *p = t.buf.as<uint32_t>();
   const hfr::Fr w = hfr::root_of_unity((unsigned)log_n);
-  pow_table(s, p, n_lo, w, hfr::ONE);
+  fr_pow_table(s, p, n_lo, w, hfr::ONE);
   t.lo = p;
   p += n_lo * 8;
   if (n_hi > 1) {
-    pow_table(s, p, n_hi, hfr::pow2k(w, (unsigned)t.lb), hfr::ONE);
+    fr_pow_table(s, p, n_hi, hfr::pow2k(w, (unsigned)t.lb), hfr::ONE);
     t.hi = p;
     p += n_hi * 8;
   }
   if (n_in) {
-    pow_table(s, p, n_in, hfr::root_of_unity(11), hfr::ONE);
+    fr_pow_table(s, p, n_in, hfr::root_of_unity(11), hfr::ONE);
     t.in = p, t.in_log = 11;
   } else {
     t.in = t.lo, t.in_log = log_n;
@@ -562,10 +522,10 @@ void FrNtt::ntt(hipStream_t cs, const void *src, void *dst, int log_n, size_t ba
       mult = hfr::RR;
     }
     const int slb = std::min(log_n, 13);
-    pow_table(cs, sh_.as<uint32_t>(), (size_t)1 << slb, base, mult);
+    fr_pow_table(cs, sh_.as<uint32_t>(), (size_t)1 << slb, base, mult);
     if (log_n > slb)
-      pow_table(cs, sh_.as<uint32_t>() + ((size_t)8 << slb), (size_t)1 << (log_n - slb),
-                hfr::pow2k(base, (unsigned)slb), hfr::ONE);
+      fr_pow_table(cs, sh_.as<uint32_t>() + ((size_t)8 << slb), (size_t)1 << (log_n - slb),
+                   hfr::pow2k(base, (unsigned)slb), hfr::ONE);
   }
   auto pend = pipe_.pending([&](int slot, size_t off, size_t cnt) {
     memcpy(static_cast<uint8_t *>(dst) + off * EL, out_.pin[slot], cnt * EL);

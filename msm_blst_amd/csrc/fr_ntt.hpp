@@ -8,6 +8,7 @@
 #include <map>
 
 #include "chunk_pipe.hpp"
+#include "host_fr.hpp"
 #include "ntt_plan.hpp"
 
 namespace msm {
@@ -52,6 +53,10 @@ class FrNtt {
   void passes(hipStream_t s, const void *d_src, void *d_dst, int log_n, size_t batch, int flags, bool shifted);
   void op_kernels(hipStream_t s, int op, void *d_dst, const void *d_a, const void *d_b, size_t n, bool b_one);
 };
+
+// out[t] = mult base^t for t < count, as the constants c 2^261 mod r the kernels multiply
+// by (canonical, 32 bytes each), queued on s: the power tables of the Fr engines
+void fr_pow_table(hipStream_t s, uint32_t *out, size_t count, const hfr::Fr &base, const hfr::Fr &mult);
 
 // register-resident Fr products per second on `device` (out[0]) and the ms spent (out[1])
 void fr_probe(int device, double out[2]);
