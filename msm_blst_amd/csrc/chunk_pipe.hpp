@@ -1,25 +1,33 @@
 // chunk_pipe.hpp -- the double-buffered chunk pipeline of the bulk engines
-// (to_affine, decode, encode, points_mult, point_segments, hash_to_curve).
+// (to_affine, decode, encode, points_mult, point_segments, hash_to_curve,
+// pairing, sig_verify, fr_ntt, fr_poly).
 // Host-only.  A call is cut into chunks; chunk k uses slot k & 1 of every
 // staging lane, so chunk k + 1 is filled and uploaded while chunk k computes
 // and chunk k - 1 is copied back and drained.  The pipe owns the copy streams
-// and the events and names the steps of the slot protocol; the loop, the
-// sizes, the fill and the kernels stay with the engine.
+// and the events and the slot protocol; the loop, the sizes, the fill, the
+// lanes and the kernels stay with the engine.
 //
-// The steps of chunk k in slot s, in the order an engine issues them, and the
-// buffer each wait guards:
-//   in_open(s)        host waits ev_h2d[s]:   chunk k - 2 has left the pinned input slot
-//   (the engine fills the pinned slot)
-//   in_gate(s)        h2d waits ev_comp[s]:   chunk k - 2's kernels have read the device input slot
-//   in_copy(s, ..)    pinned -> device on h2d (one call per upload lane)
-//   in_close(cs, s)   record ev_h2d[s] on h2d; cs waits for it
-//   out_open(cs, s)   cs waits ev_d2h[s]:     chunk k - 2 has left the device output slot
+// The steps of chunk k in slot s, in the order an engine issues them, what
+// each does, and the buffer each wait guards:
+//   upload(cs, s, fill, lanes)
+//       host waits ev_h2d[s]:   chunk k - 2 has left the pinned input slot
+//       fill()                  the engine fills the pinned slot(s)
+//       h2d waits ev_comp[s]:   chunk k - 2's kernels have read the device input slot
+//       pinned -> device on h2d, one copy per lane in the order given
+//       record ev_h2d[s] on h2d; cs waits for it
+//   out_open(cs, s)
+//       cs waits ev_d2h[s]:     chunk k - 2 has left the device output slot
 //   (the engine queues its kernels on cs)
-//   computed(cs, s)   record ev_comp[s] on cs
-//   out_gate(s)       d2h waits ev_comp[s]
-//   out_copy(s, ..)   device -> pinned on d2h (one call per download lane)
-//   out_close(s)      record ev_d2h[s] on d2h
-//   Pending::push     host waits ev_d2h of chunk k - 1 and takes it out of its pinned slot
+//   computed(cs, s)
+//       record ev_comp[s] on cs
+//   download(cs, s, pend, off, cnt, lanes)
+//       d2h waits ev_comp[s]
+//       device -> pinned on d2h, one copy per lane in the order given
+//       record ev_d2h[s] on d2h
+//       pend.push(s, off, cnt): host waits ev_d2h of chunk k - 1 and takes it out of its pinned slot
+// A lane of zero bytes issues no copy.  out_open and computed stand alone: an
+// engine whose source is device memory skips upload, one whose destination is
+// device memory skips out_open and download, and computed is never skipped.
 // begin(cs) / finish(cs) bracket a call: ev_busy is the last kernel of the
 // previous call, which may still use the buffers an engine keeps per call
 // (levels, tables, status), whatever stream that call was ordered on.
@@ -27,6 +35,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <utility>
 
 #include "engine.hpp"
@@ -133,31 +142,48 @@ class ChunkPipe {
   void begin_on_host() { MSM_HIP_CHECK(hipEventSynchronize(ev_busy_)); }
   void finish(hipStream_t cs) { MSM_HIP_CHECK(hipEventRecord(ev_busy_, cs)); }
 
-  // ---- a chunk goes up ----
-  void in_open(int slot) { MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot])); }
-  void in_gate(int slot) { MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0)); }
-  void in_copy(int slot, const Stage &st, size_t bytes) {
-    MSM_HIP_CHECK(hipMemcpyAsync(st.dev[slot].p, st.pin[slot], bytes, hipMemcpyHostToDevice, h2d_));
-  }
-  void in_close(hipStream_t cs, int slot) {
+  // One copy of a composite step: `bytes` between a pinned and a device
+  // address (the status bytes of decode and of pairing come down from a buffer
+  // that is no Stage), or slot `slot` of a Stage.  Zero bytes: no copy.
+  struct Lane {
+    void *pin;
+    void *dev;
+    size_t bytes;
+    Lane(void *pinned, void *device, size_t n) : pin(pinned), dev(device), bytes(n) {}
+    Lane(const Stage &st, int slot, size_t n) : pin(st.pin[slot]), dev(st.dev[slot].p), bytes(n) {}
+  };
+
+  // ---- a chunk goes up: fill() writes the pinned slots, the lanes carry them to the device ----
+  template <class Fill>
+  void upload(hipStream_t cs, int slot, Fill fill, std::initializer_list<Lane> lanes) {
+    MSM_HIP_CHECK(hipEventSynchronize(ev_h2d_[slot]));
+    fill();
+    MSM_HIP_CHECK(hipStreamWaitEvent(h2d_, ev_comp_[slot], 0));
+    for (const Lane &l : lanes)
+      if (l.bytes) MSM_HIP_CHECK(hipMemcpyAsync(l.dev, l.pin, l.bytes, hipMemcpyHostToDevice, h2d_));
     MSM_HIP_CHECK(hipEventRecord(ev_h2d_[slot], h2d_));
     MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_h2d_[slot], 0));
   }
 
-  // ---- its kernels, and the results come down ----
+  // ---- its kernels ----
   void out_open(hipStream_t cs, int slot) { MSM_HIP_CHECK(hipStreamWaitEvent(cs, ev_d2h_[slot], 0)); }
   void computed(hipStream_t cs, int slot) { MSM_HIP_CHECK(hipEventRecord(ev_comp_[slot], cs)); }
-  void out_gate(int slot) { MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0)); }
-  void out_copy(void *pinned, const void *device, size_t bytes) {
-    MSM_HIP_CHECK(hipMemcpyAsync(pinned, device, bytes, hipMemcpyDeviceToHost, d2h_));
+
+  // ---- the results come down; the chunk before is drained while this one runs ----
+  template <class Pend>
+  void download(hipStream_t /* cs: the copies wait for computed(cs, slot) */, int slot, Pend &pend, size_t off,
+                size_t cnt, std::initializer_list<Lane> lanes) {
+    MSM_HIP_CHECK(hipStreamWaitEvent(d2h_, ev_comp_[slot], 0));
+    for (const Lane &l : lanes)
+      if (l.bytes) MSM_HIP_CHECK(hipMemcpyAsync(l.pin, l.dev, l.bytes, hipMemcpyDeviceToHost, d2h_));
+    MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_));
+    pend.push(slot, off, cnt);
   }
-  void out_copy(int slot, const Stage &st, size_t bytes) { out_copy(st.pin[slot], st.dev[slot].p, bytes); }
-  void out_close(int slot) { MSM_HIP_CHECK(hipEventRecord(ev_d2h_[slot], d2h_)); }
   void out_wait(int slot) { MSM_HIP_CHECK(hipEventSynchronize(ev_d2h_[slot])); }
 
   // The one chunk whose results are on their way back.  push(slot, off, cnt)
-  // after out_close drains the chunk before (while this one runs) and holds
-  // this one; flush() after the loop drains the last.  take(slot, off, cnt)
+  // at the end of download drains the chunk before (while this one runs) and
+  // holds this one; flush() after the loop drains the last.  take(slot, off, cnt)
   // copies a drained chunk out of its pinned slot(s).
   template <class Take>
   class Pending {

@@ -197,11 +197,8 @@ void Decode<G>::run(hipStream_t cs, const void *src, void *dst, uint8_t *status,
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + c0 * ENC, cnt * ENC);
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, cnt * ENC);
-      pipe_.in_close(cs, slot);
+      pipe_.upload(cs, slot, [&] { memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + c0 * ENC, cnt * ENC); },
+                   {{in_, slot, cnt * ENC}});
       d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src) + c0 * ENC;
@@ -210,13 +207,9 @@ void Decode<G>::run(hipStream_t cs, const void *src, void *dst, uint8_t *status,
     d_dst = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * AFF) : out_.dev[slot].p;
     kernels(cs, d_src, d_dst, dst_[slot].as<uint8_t>(), cnt, serialized, check_group);
     pipe_.computed(cs, slot);
-    if (out_host) {
-      pipe_.out_gate(slot);
-      if (!dst_dev) pipe_.out_copy(slot, out_, cnt * AFF);
-      if (status) pipe_.out_copy(st_.pin[slot], dst_[slot].p, cnt);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
-    }
+    if (out_host)
+      pipe_.download(cs, slot, pend, c0, cnt,
+                     {{out_, slot, dst_dev ? 0 : cnt * AFF}, {st_.pin[slot], dst_[slot].p, status ? cnt : 0}});
   }
   pend.flush();
   pipe_.finish(cs);

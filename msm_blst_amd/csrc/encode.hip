@@ -92,11 +92,8 @@ void Encode<G>::run(hipStream_t cs, const void *src, void *dst, size_t n, bool j
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + c0 * PT, cnt * PT);
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, cnt * PT);
-      pipe_.in_close(cs, slot);
+      pipe_.upload(cs, slot, [&] { memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + c0 * PT, cnt * PT); },
+                   {{in_, slot, cnt * PT}});
       d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src) + c0 * PT;
@@ -109,12 +106,7 @@ void Encode<G>::run(hipStream_t cs, const void *src, void *dst, size_t n, bool j
     }
     kernels(cs, d_src, d_dst, cnt, jacobian, serialized);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, out_, cnt * ENC);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, c0, cnt, {{out_, slot, cnt * ENC}});
   }
   pend.flush();
   pipe_.finish(cs);

@@ -537,11 +537,8 @@ void FrNtt::ntt(hipStream_t cs, const void *src, void *dst, int log_n, size_t ba
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + off * EL, cnt * EL);
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, cnt * EL);
-      pipe_.in_close(cs, slot);
+      pipe_.upload(cs, slot, [&] { memcpy(in_.pin[slot], static_cast<const uint8_t *>(src) + off * EL, cnt * EL); },
+                   {{in_, slot, cnt * EL}});
       d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src) + off * EL;
@@ -554,12 +551,7 @@ void FrNtt::ntt(hipStream_t cs, const void *src, void *dst, int log_n, size_t ba
     }
     passes(cs, d_src, d_dst, log_n, nb, flags, shift != nullptr);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, out_, cnt * EL);
-      pipe_.out_close(slot);
-      pend.push(slot, off, cnt);
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, off, cnt, {{out_, slot, cnt * EL}});
   }
   pend.flush();
   pipe_.finish(cs);
@@ -637,13 +629,11 @@ void FrNtt::op(hipStream_t cs, int op, void *dst, const void *a, const void *b, 
     const void *d_a, *d_b = nullptr;
     void *d_dst;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      memcpy(in_.pin[slot], static_cast<const uint8_t *>(a) + c0 * EL, cnt * EL);
-      if (two) memcpy(inb_.pin[slot], static_cast<const uint8_t *>(b) + (b_one ? 0 : c0 * EL), b_one ? EL : cnt * EL);
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, cnt * EL);
-      if (two) pipe_.in_copy(slot, inb_, b_one ? EL : cnt * EL);
-      pipe_.in_close(cs, slot);
+      const size_t bb = !two ? 0 : b_one ? EL : cnt * EL;  // bytes of the second operand
+      pipe_.upload(cs, slot, [&] {
+        memcpy(in_.pin[slot], static_cast<const uint8_t *>(a) + c0 * EL, cnt * EL);
+        if (two) memcpy(inb_.pin[slot], static_cast<const uint8_t *>(b) + (b_one ? 0 : c0 * EL), bb);
+      }, {{in_, slot, cnt * EL}, {inb_, slot, bb}});
       d_a = in_.dev[slot].p;
       if (two) d_b = inb_.dev[slot].p;
     } else {
@@ -658,12 +648,7 @@ void FrNtt::op(hipStream_t cs, int op, void *dst, const void *a, const void *b, 
     }
     op_kernels(cs, op, d_dst, d_a, d_b, cnt, b_one);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, out_, cnt * EL);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, c0, cnt, {{out_, slot, cnt * EL}});
   }
   pend.flush();
   pipe_.finish(cs);

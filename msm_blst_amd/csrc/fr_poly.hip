@@ -347,13 +347,10 @@ void FrPoly::run(hipStream_t cs, const void *polys, const void *z, void *y, void
     const void *d_f, *d_z;
     void *d_y, *d_q = nullptr;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      memcpy(in_.pin[slot], static_cast<const uint8_t *>(polys) + off * EL, cnt * EL);
-      memcpy(inz_.pin[slot], static_cast<const uint8_t *>(z) + c0 * EL, nb * EL);
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, cnt * EL);
-      pipe_.in_copy(slot, inz_, nb * EL);
-      pipe_.in_close(cs, slot);
+      pipe_.upload(cs, slot, [&] {
+        memcpy(in_.pin[slot], static_cast<const uint8_t *>(polys) + off * EL, cnt * EL);
+        memcpy(inz_.pin[slot], static_cast<const uint8_t *>(z) + c0 * EL, nb * EL);
+      }, {{in_, slot, cnt * EL}, {inz_, slot, nb * EL}});
       d_f = in_.dev[slot].p;
       d_z = inz_.dev[slot].p;
     } else {
@@ -370,13 +367,7 @@ void FrPoly::run(hipStream_t cs, const void *polys, const void *z, void *y, void
     }
     kernels(cs, d_f, d_z, d_y, d_q, log_n, nb, flags);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, outy_, nb * EL);
-      if (q) pipe_.out_copy(slot, outq_, cnt * EL);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, nb);
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, c0, nb, {{outy_, slot, nb * EL}, {outq_, slot, q ? cnt * EL : 0}});
   }
   pend.flush();
   pipe_.finish(cs);

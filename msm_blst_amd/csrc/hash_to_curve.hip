@@ -590,21 +590,14 @@ void HashToCurve<G>::run(hipStream_t cs, int mode, const void *u, const H2cMsgs 
     const int slot = (int)(k & 1);
     const size_t b0 = hashing ? msg_begin(c0) : 0, b1 = hashing ? msg_begin(c0 + cnt) : 0;
     if (stage) {
-      pipe_.in_open(slot);  // (one event for the three upload lanes)
-      if (!src_dev) {
-        if (!hashing) memcpy(in_.pin[slot], static_cast<const uint8_t *>(u) + c0 * UB, cnt * UB);
-        else if (b1 > b0) memcpy(in_.pin[slot], m.msgs + b0, b1 - b0);
-        if (has_aug) memcpy(aug_.pin[slot], m.aug + c0 * m.aug_len, cnt * m.aug_len);
-      }
-      if (offs_up) memcpy(off_.pin[slot], m.offsets + c0, (cnt + 1) * sizeof(size_t));
-      pipe_.in_gate(slot);
-      if (!src_dev) {
-        const size_t in = hashing ? b1 - b0 : cnt * UB;
-        if (in) pipe_.in_copy(slot, in_, in);
-        if (has_aug) pipe_.in_copy(slot, aug_, cnt * m.aug_len);
-      }
-      if (offs_up) pipe_.in_copy(slot, off_, (cnt + 1) * sizeof(size_t));
-      pipe_.in_close(cs, slot);
+      // the bytes of the three upload lanes (one event for them); a chunk of empty messages sends none
+      const size_t in = src_dev ? 0 : hashing ? b1 - b0 : cnt * UB;
+      const size_t ab = !src_dev && has_aug ? cnt * m.aug_len : 0, ob = offs_up ? (cnt + 1) * sizeof(size_t) : 0;
+      pipe_.upload(cs, slot, [&] {
+        if (in) memcpy(in_.pin[slot], hashing ? m.msgs + b0 : static_cast<const uint8_t *>(u) + c0 * UB, in);
+        if (ab) memcpy(aug_.pin[slot], m.aug + c0 * m.aug_len, ab);
+        if (ob) memcpy(off_.pin[slot], m.offsets + c0, ob);
+      }, {{in_, slot, in}, {aug_, slot, ab}, {off_, slot, ob}});
     }
     if (!dst_dev) pipe_.out_open(cs, slot);
     void *d_out = dst_dev ? static_cast<void *>(static_cast<uint8_t *>(dst) + c0 * OUT) : out_.dev[slot].p;
@@ -627,12 +620,7 @@ void HashToCurve<G>::run(hipStream_t cs, int mode, const void *u, const H2cMsgs 
     }
     if (mapping) map_kernels(cs, d_u, d_out, cnt, count);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, out_, cnt * OUT);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, c0, cnt, {{out_, slot, cnt * OUT}});
   }
   pend.flush();
   pipe_.finish(cs);

@@ -301,21 +301,17 @@ void Pairing::run(hipStream_t cs, const void *p, const void *q, const size_t *o,
                   bool final_exp, bool src_dev, bool dst_dev) {
   if (!k) return;
   DeviceGuard g(dev_);
-  const size_t N = o[k], total = N - o[0];
-  // C bounds the pairs AND the segments written per chunk (a chunk of empty segments has no pairs)
-  const size_t C = std::min(std::max(total, k), std::min(pair_chunk(), (size_t)1 << 30));
-  const size_t CP = std::min(C, std::max(total, (size_t)1));  // pairs of a chunk
+  const size_t total = o[k] - o[0];
+  const SegSizes z = seg_sizes(total, k, pair_chunk());
+  const size_t C = z.C, CP = z.CP, pmax = z.pmax;
   const size_t L = pair_piece_len(CP);
-  const size_t pmax = CP + 1;  // partials of a chunk: a piece per pair where every segment is short, and the carry
-  const size_t META = pmax * sizeof(SegMeta) + C * sizeof(uint32_t);
   const bool host_out = dst && !dst_dev, back = host_out || is_one;  // something comes back per chunk
   rec_.ensure(CP * REC);
   part_.ensure(pmax * FP12S);
   res_.ensure(C * FP12S);
   if (final_exp) ws_.ensure((size_t)FE_SLOTS * C * FP12S);
   carry_.ensure(FP12S);
-  dmeta_.ensure(META);
-  plan_.ensure(META, false);
+  plan_lane_.ensure(z);
   if (!src_dev && total) {
     in_p_.ensure(CP * P_AFF);
     in_q_.ensure(CP * Q_AFF);
@@ -333,62 +329,23 @@ void Pairing::run(hipStream_t cs, const void *p, const void *q, const size_t *o,
   });
   const unsigned B = 128;
   Fp12S *part = part_.as<Fp12S>();
-  size_t j = 0, i = o[0], ck = 0;  // first segment not yet written, first pair not yet multiplied in
-  bool carry = false;              // pairs o[j] .. i - 1 of segment j are multiplied into carry_
-  for (; j < k; ++ck) {
-    // this chunk: pairs [i, e), segments [j, je) end in it
-    size_t e = std::min(i + C, N), je = j;
-    while (je < k && o[je + 1] <= e && je - j < C) ++je;
-    if (je < k && o[je + 1] <= e) e = o[je];  // C segments already: stop where the last of them ends
-    const size_t cnt = e - i, nseg = je - j;
+  plan_.begin(o, k, z, L, "pairing");
+  for (size_t ck = 0; plan_.next(); ++ck) {
+    // this chunk: pairs [i, i + cnt), segments [j, j + nseg) end in it; np partials, the carried one (pc) first
+    const size_t i = plan_.i, cnt = plan_.cnt(), j = plan_.j, nseg = plan_.nseg();
+    const size_t np = plan_.np(), npieces = plan_.npieces(), pc = plan_.pc;
     const int slot = (int)(ck & 1);
-    // ---- the plan (as point_segments.hip) ----
-    const uint32_t pc = carry ? 1 : 0;
-    meta_.clear();
-    src_.assign(nseg, ~0u);
-    if (carry) meta_.push_back(SegMeta{0, 0, 0, 0});
-    size_t run0 = 0, runseg = j, maxrun = 0, open_src = ~(size_t)0;
-    auto close_run = [&](size_t end) {  // partials [run0, end) belong to segment runseg
-      for (size_t x = run0; x < end; ++x) meta_[x].rel = (uint32_t)(x - run0), meta_[x].len = (uint32_t)(end - run0);
-      if (end > run0) {
-        maxrun = std::max(maxrun, end - run0);
-        if (runseg < je) src_[runseg - j] = (uint32_t)run0;
-        else open_src = run0;
-      }
-      run0 = end;
-    };
-    seg_cut(o, k, L, i, e, j, [&](size_t s, size_t c, size_t seg) {
-      if (seg != runseg) {
-        close_run(meta_.size());
-        runseg = seg;
-      }
-      meta_.push_back(SegMeta{(uint32_t)(s - i), (uint32_t)c, 0, 0});
-    });
-    close_run(meta_.size());
-    const size_t np = meta_.size(), npieces = np - pc;
-    if (np > pmax || nseg > C || cnt > CP) throw std::runtime_error("pairing: plan larger than its buffers");
     // ---- the plan and the sources go up ----
-    MSM_HIP_CHECK(hipEventSynchronize(ev_meta_[slot]));  // chunk k - 2's plan has left the pinned slot
-    uint8_t *pm = static_cast<uint8_t *>(plan_.pin[slot]);
-    if (np) memcpy(pm, meta_.data(), np * sizeof(SegMeta));
-    if (nseg) memcpy(pm + pmax * sizeof(SegMeta), src_.data(), nseg * sizeof(uint32_t));
-    if (np) MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.p, pm, np * sizeof(SegMeta), hipMemcpyHostToDevice, cs));
-    if (nseg)
-      MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.as<uint8_t>() + pmax * sizeof(SegMeta), pm + pmax * sizeof(SegMeta),
-                                   nseg * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
-    MSM_HIP_CHECK(hipEventRecord(ev_meta_[slot], cs));
-    const SegMeta *d_meta = dmeta_.as<SegMeta>();
-    const uint32_t *d_src = reinterpret_cast<const uint32_t *>(dmeta_.as<uint8_t>() + pmax * sizeof(SegMeta));
+    plan_lane_.send(cs, slot, plan_);
+    const SegMeta *d_meta = plan_lane_.d_meta();
+    const uint32_t *d_src = plan_lane_.d_src();
     const uint8_t *d_p = nullptr, *d_q = nullptr;
     if (cnt) {
       if (!src_dev) {
-        pipe_.in_open(slot);  // (one event for the two upload lanes)
-        memcpy(in_p_.pin[slot], static_cast<const uint8_t *>(p) + i * P_AFF, cnt * P_AFF);
-        memcpy(in_q_.pin[slot], static_cast<const uint8_t *>(q) + i * Q_AFF, cnt * Q_AFF);
-        pipe_.in_gate(slot);
-        pipe_.in_copy(slot, in_p_, cnt * P_AFF);
-        pipe_.in_copy(slot, in_q_, cnt * Q_AFF);
-        pipe_.in_close(cs, slot);
+        pipe_.upload(cs, slot, [&] {
+          memcpy(in_p_.pin[slot], static_cast<const uint8_t *>(p) + i * P_AFF, cnt * P_AFF);
+          memcpy(in_q_.pin[slot], static_cast<const uint8_t *>(q) + i * Q_AFF, cnt * Q_AFF);
+        }, {{in_p_, slot, cnt * P_AFF}, {in_q_, slot, cnt * Q_AFF}});  // (one event for the two lanes)
         d_p = in_p_.dev[slot].as<uint8_t>();
         d_q = in_q_.dev[slot].as<uint8_t>();
       } else {
@@ -404,11 +361,11 @@ void Pairing::run(hipStream_t cs, const void *p, const void *q, const size_t *o,
       hipLaunchKernelGGL(k_pair_init, dim3(nblk(cnt * 2, B)), dim3(B), 0, cs, reinterpret_cast<const uint64_t *>(d_p),
                          reinterpret_cast<const uint64_t *>(d_q), cnt, rec_.as<PairRec>());
       MSM_HIP_CHECK(hipGetLastError());
-      if (carry) MSM_HIP_CHECK(hipMemcpyAsync(part, carry_.p, FP12S, hipMemcpyDeviceToDevice, cs));
+      if (pc) MSM_HIP_CHECK(hipMemcpyAsync(part, carry_.p, FP12S, hipMemcpyDeviceToDevice, cs));
       hipLaunchKernelGGL(k_pair_miller, dim3(nblk(npieces * 2, B)), dim3(B), 0, cs, rec_.as<PairRec>(), d_meta + pc,
                          part + pc, npieces);
       MSM_HIP_CHECK(hipGetLastError());
-      for (size_t step = 1; step < maxrun; step *= 2) {
+      for (size_t step = 1; step < plan_.maxrun; step *= 2) {
         hipLaunchKernelGGL(k_pair_merge, dim3(nblk(np * 2, B)), dim3(B), 0, cs, part, d_meta, np, (uint32_t)step);
         MSM_HIP_CHECK(hipGetLastError());
       }
@@ -419,18 +376,12 @@ void Pairing::run(hipStream_t cs, const void *p, const void *q, const size_t *o,
       MSM_HIP_CHECK(hipGetLastError());
       finish_kernels(cs, nseg, d_dst, d_st, final_exp);
     }
-    carry = open_src != ~(size_t)0;
-    if (carry) MSM_HIP_CHECK(hipMemcpyAsync(carry_.p, part + open_src, FP12S, hipMemcpyDeviceToDevice, cs));
+    // a segment stays open: what this chunk multiplied of it goes into the next one
+    if (plan_.carry()) MSM_HIP_CHECK(hipMemcpyAsync(carry_.p, part + plan_.open_src, FP12S, hipMemcpyDeviceToDevice, cs));
     pipe_.computed(cs, slot);
-    if (back) {
-      pipe_.out_gate(slot);
-      if (host_out && nseg) pipe_.out_copy(slot, out_, nseg * GT);
-      if (is_one && nseg) pipe_.out_copy(st_.pin[slot], st_dev_[slot].p, nseg);
-      pipe_.out_close(slot);
-      pend.push(slot, j, nseg);  // chunk k - 1 is drained while chunk k runs
-    }
-    i = e;
-    j = je;
+    if (back)
+      pipe_.download(cs, slot, pend, j, nseg,
+                     {{out_, slot, host_out ? nseg * GT : 0}, {st_.pin[slot], st_dev_[slot].p, is_one ? nseg : 0}});
   }
   pend.flush();  // (nothing is held where no chunk ran)
   pipe_.finish(cs);
@@ -462,11 +413,8 @@ void Pairing::run_final_exp(hipStream_t cs, const void *src, size_t n, void *dst
     const int slot = (int)(ck & 1);
     const void *d_src;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      memcpy(in_q_.pin[slot], static_cast<const uint8_t *>(src) + c0 * GT, cnt * GT);
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_q_, cnt * GT);
-      pipe_.in_close(cs, slot);
+      pipe_.upload(cs, slot, [&] { memcpy(in_q_.pin[slot], static_cast<const uint8_t *>(src) + c0 * GT, cnt * GT); },
+                   {{in_q_, slot, cnt * GT}});
       d_src = in_q_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src) + c0 * GT;
@@ -478,13 +426,9 @@ void Pairing::run_final_exp(hipStream_t cs, const void *src, size_t n, void *dst
     MSM_HIP_CHECK(hipGetLastError());
     finish_kernels(cs, cnt, d_dst, is_one ? st_dev_[slot].as<uint8_t>() : nullptr, true);
     pipe_.computed(cs, slot);
-    if (back) {
-      pipe_.out_gate(slot);
-      if (host_out) pipe_.out_copy(slot, out_, cnt * GT);
-      if (is_one) pipe_.out_copy(st_.pin[slot], st_dev_[slot].p, cnt);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);
-    }
+    if (back)
+      pipe_.download(cs, slot, pend, c0, cnt,
+                     {{out_, slot, host_out ? cnt * GT : 0}, {st_.pin[slot], st_dev_[slot].p, is_one ? cnt : 0}});
   }
   pend.flush();
   pipe_.finish(cs);

@@ -8,8 +8,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <vector>
-
 #include "chunk_pipe.hpp"
 #include "point_segments.hpp"
 #include "segments_plan.hpp"
@@ -51,7 +49,7 @@ class Pairing {
  public:
   static constexpr size_t P_AFF = 96, Q_AFF = 192, GT = 576, FP12S = 672, REC = 680;
   static constexpr int FE_SLOTS = 5;
-  explicit Pairing(int device) : dev_(device), ev_meta_(device), pipe_(device) {}
+  explicit Pairing(int device) : dev_(device), plan_lane_(device), pipe_(device) {}
   // dst[j] = E(segment j) for j < k, o = offsets (host, k + 1 values,
   // non-decreasing); with final_exp false the product of the Miller values.
   // p and q are both host or both device memory (src_dev) and are indexed from
@@ -64,19 +62,18 @@ class Pairing {
   // dst[i] = fe(src[i]) for i < n (blst Fp12 values)
   void run_final_exp(hipStream_t cs, const void *src, size_t n, void *dst, uint8_t *is_one, bool src_dev, bool dst_dev);
   size_t device_bytes() const {
-    return rec_.bytes + part_.bytes + res_.bytes + ws_.bytes + carry_.bytes + dmeta_.bytes + st_dev_[0].bytes +
-           st_dev_[1].bytes + in_p_.device_bytes() + in_q_.device_bytes() + out_.device_bytes();
+    return rec_.bytes + part_.bytes + res_.bytes + ws_.bytes + carry_.bytes + plan_lane_.device_bytes() +
+           st_dev_[0].bytes + st_dev_[1].bytes + in_p_.device_bytes() + in_q_.device_bytes() + out_.device_bytes();
   }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf rec_, part_, res_, ws_, carry_, dmeta_, st_dev_[2];
-  Stage in_p_, in_q_, out_, st_, plan_;  // st_, plan_: pinned only
-  std::vector<SegMeta> meta_;            // the plan of the chunk being queued
-  std::vector<uint32_t> src_;            // per segment written by the chunk: the partial that holds its value, or ~0 (empty)
-  EventPair ev_meta_;                    // the plan of chunk k - 2 has left its pinned slot
-  ChunkPipe pipe_;                       // (last: it waits for the queued work before the buffers go)
+  DevBuf rec_, part_, res_, ws_, carry_, st_dev_[2];
+  Stage in_p_, in_q_, out_, st_;  // st_: pinned only
+  SegPlanner plan_;               // the plan of the chunk being queued (segments_plan.hpp)
+  SegPlanLane plan_lane_;         // and its way to the device (point_segments.hpp)
+  ChunkPipe pipe_;                // (last: it waits for the queued work before the buffers go)
   // values res_[0 .. n) -> dst / verdicts (device pointers, either may be NULL)
   void finish_kernels(hipStream_t s, size_t n, void *d_dst, uint8_t *d_st, bool final_exp);
 };

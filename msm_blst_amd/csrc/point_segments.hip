@@ -207,22 +207,18 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
     throw std::runtime_error("point_segments: bad nbits / stride");
   DeviceGuard g(dev_);
   const size_t nb = msm ? (size_t)(nbits + 7) / 8 : 0;
-  const size_t N = o[k], total = N - o[0];
-  // C bounds the points AND the segments written per chunk (a chunk of empty segments has no points)
-  const size_t C = std::min(std::max(total, k), std::min(seg_chunk(G), (size_t)1 << 30));
-  const size_t CP = std::min(C, std::max(total, (size_t)1));  // points of a chunk
+  const size_t total = o[k] - o[0];
+  const SegSizes z = seg_sizes(total, k, seg_chunk(G));
+  const size_t C = z.C, CP = z.CP, pmax = z.pmax;
   const size_t L = seg_piece_len(CP, G);
   const size_t PB = CP * AFF;      // the points in a staged slot; the scalars follow
   const size_t IN = PB + CP * nb;  // (staged scalars are packed: nb bytes apart)
-  const size_t pmax = CP + 1;  // partials of a chunk: a piece per point where every segment is short, and the carry
-  const size_t META = pmax * sizeof(SegMeta) + C * sizeof(uint32_t);
   if (msm) rows_.ensure(PM_ROWS * CP * ROW);
   xz_.ensure(std::max(msm ? (size_t)(PM_ROWS - 1) * CP : 0, pmax) * XYZZ);
   res_.ensure(C * XYZZ);
   lv_.ensure(std::max(msm ? ta_level_elems((size_t)(PM_ROWS - 1) * CP) : 0, ta_level_elems(C)) * ELEM);
   carry_.ensure(XYZZ);
-  dmeta_.ensure(META);
-  plan_.ensure(META, false);
+  plan_lane_.ensure(z);
   if (!src_dev && total) in_.ensure(IN);
   if (!dst_dev) out_.ensure(C * AFF);
   pipe_.begin(cs);  // the table, partial and level buffers of the previous call
@@ -231,69 +227,31 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
   });
   const unsigned B = 128;
   Xyzz<SF> *part = xz_.as<Xyzz<SF>>();
-  size_t j = 0, i = o[0], ck = 0;  // first segment not yet written, first point not yet summed
-  bool carry = false;              // points o[j] .. i - 1 of segment j are summed in carry_
-  for (; j < k; ++ck) {
-    // this chunk: points [i, e), segments [j, je) end in it
-    size_t e = std::min(i + C, N), je = j;
-    while (je < k && o[je + 1] <= e && je - j < C) ++je;
-    if (je < k && o[je + 1] <= e) e = o[je];  // C segments already: stop where the last of them ends
-    const size_t cnt = e - i, nseg = je - j;
+  plan_.begin(o, k, z, L, "point_segments");
+  for (size_t ck = 0; plan_.next(); ++ck) {
+    // this chunk: points [i, i + cnt), segments [j, j + nseg) end in it; np partials, the carried one (pc) first
+    const size_t i = plan_.i, cnt = plan_.cnt(), j = plan_.j, nseg = plan_.nseg();
+    const size_t np = plan_.np(), npieces = plan_.npieces(), pc = plan_.pc;
     const int slot = (int)(ck & 1);
-    // ---- the plan ----
-    const uint32_t pc = carry ? 1 : 0;
-    meta_.clear();
-    src_.assign(nseg, ~0u);
-    if (carry) meta_.push_back(SegMeta{0, 0, 0, 0});
-    size_t run0 = 0, runseg = j, maxrun = 0, open_src = ~(size_t)0;
-    auto close_run = [&](size_t end) {  // partials [run0, end) belong to segment runseg
-      for (size_t p = run0; p < end; ++p) meta_[p].rel = (uint32_t)(p - run0), meta_[p].len = (uint32_t)(end - run0);
-      if (end > run0) {
-        maxrun = std::max(maxrun, end - run0);
-        if (runseg < je) src_[runseg - j] = (uint32_t)run0;
-        else open_src = run0;
-      }
-      run0 = end;
-    };
-    seg_cut(o, k, L, i, e, j, [&](size_t s, size_t c, size_t seg) {
-      if (seg != runseg) {
-        close_run(meta_.size());
-        runseg = seg;
-      }
-      meta_.push_back(SegMeta{(uint32_t)(s - i), (uint32_t)c, 0, 0});
-    });
-    close_run(meta_.size());
-    const size_t np = meta_.size(), npieces = np - pc;
-    if (np > pmax || nseg > C || cnt > CP) throw std::runtime_error("point_segments: plan larger than its buffers");
     // ---- the plan and the sources go up ----
-    MSM_HIP_CHECK(hipEventSynchronize(ev_meta_[slot]));  // chunk k - 2's plan has left the pinned slot
-    uint8_t *pm = static_cast<uint8_t *>(plan_.pin[slot]);
-    if (np) memcpy(pm, meta_.data(), np * sizeof(SegMeta));
-    if (nseg) memcpy(pm + pmax * sizeof(SegMeta), src_.data(), nseg * sizeof(uint32_t));
-    if (np) MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.p, pm, np * sizeof(SegMeta), hipMemcpyHostToDevice, cs));
-    if (nseg)
-      MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.as<uint8_t>() + pmax * sizeof(SegMeta), pm + pmax * sizeof(SegMeta),
-                                   nseg * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
-    MSM_HIP_CHECK(hipEventRecord(ev_meta_[slot], cs));
-    const SegMeta *d_meta = dmeta_.as<SegMeta>();
-    const uint32_t *d_src = reinterpret_cast<const uint32_t *>(dmeta_.as<uint8_t>() + pmax * sizeof(SegMeta));
+    plan_lane_.send(cs, slot, plan_);
+    const SegMeta *d_meta = plan_lane_.d_meta();
+    const uint32_t *d_src = plan_lane_.d_src();
     const uint8_t *d_pts = nullptr, *d_sc = nullptr;
     size_t d_stride = stride;
     if (cnt) {
       if (!src_dev) {
-        pipe_.in_open(slot);
-        uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
-        memcpy(w, static_cast<const uint8_t *>(points) + i * AFF, cnt * AFF);
-        if (msm) {
-          const uint8_t *sc = scalars + i * stride;
-          if (stride == nb) memcpy(w + PB, sc, cnt * nb);
-          else  // only the nb bytes of each scalar: nothing past the last one is read, and the slot stays small
-            for (size_t q = 0; q < cnt; ++q) memcpy(w + PB + q * nb, sc + q * stride, nb);
-          d_stride = nb;
-        }
-        pipe_.in_gate(slot);
-        pipe_.in_copy(slot, in_, PB + cnt * nb);
-        pipe_.in_close(cs, slot);
+        pipe_.upload(cs, slot, [&] {
+          uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
+          memcpy(w, static_cast<const uint8_t *>(points) + i * AFF, cnt * AFF);
+          if (msm) {
+            const uint8_t *sc = scalars + i * stride;
+            if (stride == nb) memcpy(w + PB, sc, cnt * nb);
+            else  // only the nb bytes of each scalar: nothing past the last one is read, and the slot stays small
+              for (size_t q = 0; q < cnt; ++q) memcpy(w + PB + q * nb, sc + q * stride, nb);
+          }
+        }, {{in_, slot, PB + cnt * nb}});
+        if (msm) d_stride = nb;
         d_pts = in_.dev[slot].as<uint8_t>();
         d_sc = d_pts + PB;
       } else {
@@ -317,7 +275,7 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
         ta_tree<G>(cs, lv_.p, lv_.bytes, TA_XYZZ_ROWS, xz_.p, rows_.as<Aff<SF>>() + cnt, (size_t)(PM_ROWS - 1) * cnt);
       }
       // (the partials overwrite the xyzz multiples, which the rows no longer need)
-      if (carry) MSM_HIP_CHECK(hipMemcpyAsync(part, carry_.p, XYZZ, hipMemcpyDeviceToDevice, cs));
+      if (pc) MSM_HIP_CHECK(hipMemcpyAsync(part, carry_.p, XYZZ, hipMemcpyDeviceToDevice, cs));
       if (msm)
         hipLaunchKernelGGL(k_ps_straus<G>, dim3(nblk(npieces * G, B)), dim3(B), 0, cs,
                            (const Aff<SF> *)rows_.as<Aff<SF>>(), cnt, d_sc, d_stride, nbits, d_meta + pc, part + pc,
@@ -326,7 +284,7 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
         hipLaunchKernelGGL(k_ps_sum<G>, dim3(nblk(npieces * G, B)), dim3(B), 0, cs,
                            reinterpret_cast<const uint64_t *>(d_pts), d_meta + pc, part + pc, npieces);
       MSM_HIP_CHECK(hipGetLastError());
-      for (size_t step = 1; step < maxrun; step *= 2) {
+      for (size_t step = 1; step < plan_.maxrun; step *= 2) {
         hipLaunchKernelGGL(k_ps_merge<G>, dim3(nblk(np * G, B)), dim3(B), 0, cs, part, d_meta, np, (uint32_t)step);
         MSM_HIP_CHECK(hipGetLastError());
       }
@@ -337,17 +295,10 @@ void PointSegments<G>::run(hipStream_t cs, const void *points, const uint8_t *sc
       MSM_HIP_CHECK(hipGetLastError());
       ta_tree<G>(cs, lv_.p, lv_.bytes, TA_XYZZ_BLST, res_.p, d_dst, nseg);
     }
-    carry = open_src != ~(size_t)0;
-    if (carry) MSM_HIP_CHECK(hipMemcpyAsync(carry_.p, part + open_src, XYZZ, hipMemcpyDeviceToDevice, cs));
+    // a segment stays open: what this chunk summed of it goes into the next one
+    if (plan_.carry()) MSM_HIP_CHECK(hipMemcpyAsync(carry_.p, part + plan_.open_src, XYZZ, hipMemcpyDeviceToDevice, cs));
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      if (nseg) pipe_.out_copy(slot, out_, nseg * AFF);
-      pipe_.out_close(slot);
-      pend.push(slot, j, nseg);  // chunk k - 1 is drained while chunk k runs
-    }
-    i = e;
-    j = je;
+    if (!dst_dev) pipe_.download(cs, slot, pend, j, nseg, {{out_, slot, nseg * AFF}});
   }
   pend.flush();  // (nothing is held where no chunk ran)
   pipe_.finish(cs);

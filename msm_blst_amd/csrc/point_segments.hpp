@@ -8,17 +8,44 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <vector>
+#include <cstring>
 
 #include "chunk_pipe.hpp"
 #include "segments_plan.hpp"
 
 namespace msm {
 
-// what a lane (pair) of the kernels knows about its partial sum
-struct SegMeta {
-  uint32_t start, count;  // the piece: first point (relative to the chunk) and points; the carried partial has none
-  uint32_t rel, len;      // position in the run of partials of its segment, and the length of that run
+// The lane of a chunk's plan (SegPlanner), shared with pairing.hip: two pinned
+// slots with events of their own, and one device copy, written on the compute
+// stream in front of the chunk's kernels.
+class SegPlanLane {
+ public:
+  explicit SegPlanLane(int device) : ev_(device) {}
+  void ensure(const SegSizes &z) {
+    dmeta_.ensure(z.META);
+    pin_.ensure(z.META, false);
+    src_at_ = z.pmax * sizeof(SegMeta);
+  }
+  // the plan of the chunk in `slot` goes up on cs
+  void send(hipStream_t cs, int slot, const SegPlanner &pl) {
+    const size_t mb = pl.np() * sizeof(SegMeta), sb = pl.nseg() * sizeof(uint32_t);
+    MSM_HIP_CHECK(hipEventSynchronize(ev_[slot]));  // chunk k - 2's plan has left the pinned slot
+    uint8_t *pm = static_cast<uint8_t *>(pin_.pin[slot]);
+    if (mb) memcpy(pm, pl.meta.data(), mb);
+    if (sb) memcpy(pm + src_at_, pl.src.data(), sb);
+    if (mb) MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.p, pm, mb, hipMemcpyHostToDevice, cs));
+    if (sb) MSM_HIP_CHECK(hipMemcpyAsync(dmeta_.as<uint8_t>() + src_at_, pm + src_at_, sb, hipMemcpyHostToDevice, cs));
+    MSM_HIP_CHECK(hipEventRecord(ev_[slot], cs));
+  }
+  const SegMeta *d_meta() const { return dmeta_.as<SegMeta>(); }
+  const uint32_t *d_src() const { return reinterpret_cast<const uint32_t *>(dmeta_.as<uint8_t>() + src_at_); }
+  size_t device_bytes() const { return dmeta_.bytes; }
+
+ private:
+  DevBuf dmeta_;
+  Stage pin_;          // pinned only
+  size_t src_at_ = 0;  // the sources follow the pmax entries of the call
+  EventPair ev_;       // (last: it waits for the copies before the slots go)
 };
 
 // One engine: the table of a chunk (xyzz multiples, then their affine rows; the
@@ -32,7 +59,7 @@ template <int G>
 class PointSegments {
  public:
   static constexpr size_t AFF = 96 * G, ROW = 112 * G, XYZZ = 224 * G, ELEM = 56 * G;
-  explicit PointSegments(int device) : dev_(device), ev_meta_(device), pipe_(device) {}
+  explicit PointSegments(int device) : dev_(device), plan_lane_(device), pipe_(device) {}
   // dst[j] = sum_{o[j] <= i < o[j + 1]} [k_i] P_i for j < k, o = offsets (host,
   // k + 1 values, non-decreasing).  k_i = the low nbits bits of the
   // little-endian scalar at scalars + i stride (0 < nbits <= 256, stride >=
@@ -44,19 +71,18 @@ class PointSegments {
   void run(hipStream_t cs, const void *points, const uint8_t *scalars, const size_t *offsets, size_t k, void *dst,
            int nbits, size_t stride, bool src_dev, bool dst_dev);
   size_t device_bytes() const {
-    return xz_.bytes + rows_.bytes + res_.bytes + lv_.bytes + carry_.bytes + dmeta_.bytes + in_.device_bytes() +
-           out_.device_bytes();
+    return xz_.bytes + rows_.bytes + res_.bytes + lv_.bytes + carry_.bytes + plan_lane_.device_bytes() +
+           in_.device_bytes() + out_.device_bytes();
   }
   int device() const { return dev_; }
 
  private:
   int dev_;
-  DevBuf xz_, rows_, res_, lv_, carry_, dmeta_;
-  Stage in_, out_, plan_;      // plan_: pinned only, copied into dmeta_ on the compute stream
-  std::vector<SegMeta> meta_;  // the plan of the chunk being queued
-  std::vector<uint32_t> src_;  // per segment written by the chunk: the partial that holds its sum, or ~0 (empty)
-  EventPair ev_meta_;          // the plan of chunk k - 2 has left its pinned slot
-  ChunkPipe pipe_;             // (last: it waits for the queued work before the buffers go)
+  DevBuf xz_, rows_, res_, lv_, carry_;
+  Stage in_, out_;
+  SegPlanner plan_;        // the plan of the chunk being queued
+  SegPlanLane plan_lane_;  // and its way to the device
+  ChunkPipe pipe_;         // (last: it waits for the queued work before the buffers go)
 };
 
 }  // namespace msm

@@ -148,17 +148,15 @@ void PointsMult<G>::run(hipStream_t cs, const void *points, const uint8_t *scala
     size_t d_stride = stride;
     void *d_dst;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
-      memcpy(w, static_cast<const uint8_t *>(points) + (one_point ? 0 : c0 * AFF), np * AFF);
-      const uint8_t *sc = scalars + c0 * stride;
-      if (stride == nb) memcpy(w + PB, sc, cnt * nb);
-      else  // only the nb bytes of each scalar: nothing past the last one is read, and the slot stays small
-        for (size_t i = 0; i < cnt; ++i) memcpy(w + PB + i * nb, sc + i * stride, nb);
+      pipe_.upload(cs, slot, [&] {
+        uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
+        memcpy(w, static_cast<const uint8_t *>(points) + (one_point ? 0 : c0 * AFF), np * AFF);
+        const uint8_t *sc = scalars + c0 * stride;
+        if (stride == nb) memcpy(w + PB, sc, cnt * nb);
+        else  // only the nb bytes of each scalar: nothing past the last one is read, and the slot stays small
+          for (size_t i = 0; i < cnt; ++i) memcpy(w + PB + i * nb, sc + i * stride, nb);
+      }, {{in_, slot, PB + cnt * nb}});
       d_stride = nb;
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, PB + cnt * nb);
-      pipe_.in_close(cs, slot);
       d_pts = in_.dev[slot].as<uint8_t>();
       d_sc = d_pts + PB;
     } else {
@@ -174,12 +172,7 @@ void PointsMult<G>::run(hipStream_t cs, const void *points, const uint8_t *scala
     if (!one_point || k == 0) table(cs, d_pts, np);  // one point: its rows serve every chunk
     ladder(cs, np, d_sc, d_dst, cnt, nbits, d_stride);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, out_, cnt * AFF);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, c0, cnt, {{out_, slot, cnt * AFF}});
   }
   pend.flush();
   pipe_.finish(cs);

@@ -129,16 +129,12 @@ void SigVerify<PKG>::run(hipStream_t cs, const SigCall &c, uint8_t *status) {
       if (nk) in_k_.ensure(nk * KIN);
       if (ns) in_s_.ensure(ns * SIN);
       if (weighted && nr) in_w_.ensure(nr * nb);
-      pipe_.in_open(0);
-      if (nk) memcpy(in_k_.pin[0], d_kin, nk * KIN);
-      if (ns) memcpy(in_s_.pin[0], d_sin, ns * SIN);
-      if (weighted)
-        for (size_t i = 0; i < nr; ++i) memcpy(static_cast<uint8_t *>(in_w_.pin[0]) + i * nb, d_w + i * c.stride, nb);
-      pipe_.in_gate(0);
-      if (nk) pipe_.in_copy(0, in_k_, nk * KIN);
-      if (ns) pipe_.in_copy(0, in_s_, ns * SIN);
-      if (weighted && nr) pipe_.in_copy(0, in_w_, nr * nb);
-      pipe_.in_close(cs, 0);
+      pipe_.upload(cs, 0, [&] {
+        if (nk) memcpy(in_k_.pin[0], d_kin, nk * KIN);
+        if (ns) memcpy(in_s_.pin[0], d_sin, ns * SIN);
+        if (weighted)
+          for (size_t i = 0; i < nr; ++i) memcpy(static_cast<uint8_t *>(in_w_.pin[0]) + i * nb, d_w + i * c.stride, nb);
+      }, {{in_k_, 0, nk * KIN}, {in_s_, 0, ns * SIN}, {in_w_, 0, nr * nb}});  // (nb is 0 unless weighted)
       d_kin = in_k_.dev[0].as<uint8_t>(), d_sin = in_s_.dev[0].as<uint8_t>();
       if (weighted) d_w = in_w_.dev[0].as<uint8_t>(), wstride = nb;
     }
@@ -247,11 +243,7 @@ void GroupScreen<G>::run(hipStream_t cs, const void *src, uint8_t *in_group, siz
     const size_t cnt = std::min(C, n - c0);
     const void *d_src = static_cast<const uint8_t *>(src) + c0 * AFF;
     if (!src_dev) {
-      pipe_.in_open(0);
-      memcpy(in_.pin[0], d_src, cnt * AFF);
-      pipe_.in_gate(0);
-      pipe_.in_copy(0, in_, cnt * AFF);
-      pipe_.in_close(cs, 0);
+      pipe_.upload(cs, 0, [&] { memcpy(in_.pin[0], d_src, cnt * AFF); }, {{in_, 0, cnt * AFF}});
       d_src = in_.dev[0].p;
     }
     screen<G>(cs, d_src, nullptr, code_.as<uint8_t>(), cnt);

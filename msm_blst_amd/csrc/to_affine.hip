@@ -354,18 +354,16 @@ void ToAffine<G>::run(hipStream_t cs, const void *src_dev_ptr, const std::vector
     const void *d_src;
     void *d_dst;
     if (!src_dev) {
-      pipe_.in_open(slot);
-      uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
-      for (size_t left = cnt; left;) {  // the gather writes straight into pinned memory
-        if (ri >= runs.size()) throw std::runtime_error("to_affine: pointer runs do not cover the points");
-        const size_t take = std::min(left, runs[ri].count - roff);
-        memcpy(w, runs[ri].p + roff * JAC, take * JAC);
-        w += take * JAC, left -= take, roff += take;
-        if (roff == runs[ri].count) ++ri, roff = 0;
-      }
-      pipe_.in_gate(slot);
-      pipe_.in_copy(slot, in_, cnt * JAC);
-      pipe_.in_close(cs, slot);
+      pipe_.upload(cs, slot, [&] {
+        uint8_t *w = static_cast<uint8_t *>(in_.pin[slot]);
+        for (size_t left = cnt; left;) {  // the gather writes straight into pinned memory
+          if (ri >= runs.size()) throw std::runtime_error("to_affine: pointer runs do not cover the points");
+          const size_t take = std::min(left, runs[ri].count - roff);
+          memcpy(w, runs[ri].p + roff * JAC, take * JAC);
+          w += take * JAC, left -= take, roff += take;
+          if (roff == runs[ri].count) ++ri, roff = 0;
+        }
+      }, {{in_, slot, cnt * JAC}});
       d_src = in_.dev[slot].p;
     } else {
       d_src = static_cast<const uint8_t *>(src_dev_ptr) + c0 * JAC;
@@ -378,12 +376,7 @@ void ToAffine<G>::run(hipStream_t cs, const void *src_dev_ptr, const std::vector
     }
     kernels(cs, d_src, d_dst, cnt);
     pipe_.computed(cs, slot);
-    if (!dst_dev) {
-      pipe_.out_gate(slot);
-      pipe_.out_copy(slot, out_, cnt * AFF);
-      pipe_.out_close(slot);
-      pend.push(slot, c0, cnt);  // chunk k - 1 is drained while chunk k runs
-    }
+    if (!dst_dev) pipe_.download(cs, slot, pend, c0, cnt, {{out_, slot, cnt * AFF}});
   }
   pend.flush();
   pipe_.finish(cs);

@@ -1,7 +1,8 @@
-"""What the six bulk engines share (csrc/chunk_pipe.hpp: the two staging slots,
-their events, the hand-over from one call to the next) on an MI355X, through
-every one of their entry points: ps_to_affine, ps_decode, ps_encode, ps_mult,
-ps_msm_segments and ps_hash_to_curve, G1 and G2.
+"""What the bulk engines share (csrc/chunk_pipe.hpp: the two staging slots, their
+events, the hand-over from one call to the next) on an MI355X, through their
+entry points: ps_to_affine, ps_decode, ps_encode, ps_mult, ps_msm_segments and
+ps_hash_to_curve, G1 and G2, and the ones that have no group: fr_op, fr_ntt,
+fr_eval_quotient, ps_pairing_segments and ps_final_exp.
 
 The expected value of a case is the same call unchunked, host to host, computed
 once; the per-operation GPU tests tie that call to the oracles.  Every
@@ -10,16 +11,23 @@ comparison is byte for byte.
 import pytest
 
 import enc_inputs as ei
+import fr_inputs as fi
 import h2c_inputs as h
 import jac_inputs as ji
+import kzg_inputs as ki
 import mult_inputs as mi
+import pairing_inputs as pi
 import seg_inputs as si
 
 pytestmark = pytest.mark.gpu
 
 N = 300  # entries: four chunks of 96 (both slots used twice, the last chunk ragged)
 OPS = {"to_affine": "MSM_TO_AFFINE_CHUNK", "decode": "MSM_DECODE_CHUNK", "encode": "MSM_ENCODE_CHUNK",
-       "mult": "MSM_POINTS_MULT_CHUNK", "segments": "MSM_POINTS_SEGMENTS_CHUNK", "hash": "MSM_H2C_CHUNK"}
+       "mult": "MSM_POINTS_MULT_CHUNK", "segments": "MSM_POINTS_SEGMENTS_CHUNK", "hash": "MSM_H2C_CHUNK",
+       "fr_mul": "MSM_NTT_CHUNK", "fr_inv": "MSM_NTT_CHUNK", "ntt": "MSM_NTT_CHUNK", "poly": "MSM_POLY_CHUNK",
+       "pairing": "MSM_PAIRING_CHUNK", "final_exp": "MSM_PAIRING_CHUNK"}
+GROUPLESS = ("fr_mul", "fr_inv", "ntt", "poly", "pairing", "final_exp")  # one case each (group None)
+LOG_N, BATCH = 5, 10  # ntt, poly: three transforms of 32 per chunk of 96, four chunks, the last of one
 PATHS = ["h2h", "h2d", "d2h", "d2d"]  # source memory, destination memory
 SEG_LENGTHS = [129, 15, 0, 47, 1, 0, 0, 10, 98]  # 300 points: one segment over three chunks of 96, empty ones
 _CASES = {}
@@ -64,7 +72,41 @@ def segments_case(m, group, lengths, with_scalars=True):
         m.ps_msm_segments(group, s[0], s[1], o, nbits=64, stride=8, src_on_device=dev, dst=dst, stream=stream), b""))
 
 
+def build_groupless(m, op):
+    F, n = m.FR_BYTES, BATCH << LOG_N
+    if op == "fr_mul":
+        return Case([fi.pack(fi.rand_values(N, 21)), fi.pack(fi.rand_values(N, 22))], N * F, lambda s, dev, dst, stream: (
+            m.fr_op("mul", s[0], s[1], N, src_on_device=dev, dst=dst, stream=stream), b""))
+    if op == "fr_inv":  # (adds the level buffer of the batch inversion; a zero among the values)
+        vals = fi.special_values()
+        return Case([fi.pack(vals + fi.rand_values(N - len(vals), 23))], N * F, lambda s, dev, dst, stream: (
+            m.fr_op("inv", s[0], None, N, src_on_device=dev, dst=dst, stream=stream), b""))
+    if op == "ntt":
+        return Case([fi.pack(fi.rand_values(n, 24))], n * F, lambda s, dev, dst, stream: (
+            m.fr_ntt(s[0], LOG_N, BATCH, src_on_device=dev, dst=dst, stream=stream), b""))
+    if op == "poly":  # y then q in one output; two of the points lie on the domain
+        z = fi.rand_values(BATCH, 26)
+        z[3], z[9] = ki.domain(LOG_N)[5], ki.domain(LOG_N)[0]
+
+        def call(s, dev, dst, stream):
+            if dst is None:
+                y, q = m.fr_eval_quotient(s[0], s[1], LOG_N, BATCH, src_on_device=dev, stream=stream)
+                return y + q, b""
+            return m.fr_eval_quotient(s[0], s[1], LOG_N, BATCH, src_on_device=dev, y_dst=dst, q_dst=dst + BATCH * F,
+                                      stream=stream), b""
+        return Case([fi.pack(fi.rand_values(n, 25)), fi.pack(z)], (BATCH + n) * F, call)
+    if op == "pairing":
+        o = si.offsets_of(SEG_LENGTHS)
+        return Case(list(pi.pair_bytes(pi.cyclic(N))), len(SEG_LENGTHS) * m.FP12_BYTES, lambda s, dev, dst, stream: (
+            m.ps_pairing_segments(s[0], s[1], o, src_on_device=dev, dst=dst, stream=stream), b""))
+    assert op == "final_exp"
+    return Case([b"".join(pi.fp12_bytes(f) for f in pi.random_fp12(N, 27))], N * m.FP12_BYTES,
+                lambda s, dev, dst, stream: (m.ps_final_exp(s[0], N, src_on_device=dev, dst=dst, stream=stream), b""))
+
+
 def build(m, op, group):
+    if group is None:
+        return build_groupless(m, op)
     A = ei.AFF[group]
     aff = bytes(m.fixed_points(group, N))
     if op == "to_affine":
@@ -107,8 +149,9 @@ def case(m, request, monkeypatch):
     return c, OPS[op]
 
 
-ALL = pytest.mark.parametrize("case", [(op, g) for op in OPS for g in (1, 2)], indirect=True,
-                              ids=[f"{op}-g{g}" for op in OPS for g in (1, 2)])
+_PARAMS = [(op, g) for op in OPS for g in ((None,) if op in GROUPLESS else (1, 2))]
+ALL = pytest.mark.parametrize("case", _PARAMS, indirect=True,
+                              ids=[op if g is None else f"{op}-g{g}" for op, g in _PARAMS])
 
 
 class Device:

@@ -235,9 +235,6 @@ def test_piece_rule(m, monkeypatch):
 
 PLAN_MAIN = r"""
 #include <stdio.h>
-#include <vector>
-#include "segments_plan.hpp"
-using namespace msm;
 int main() {
   const size_t Ls[] = {1, 3, 64};
   size_t total = 0;
@@ -275,8 +272,115 @@ int main() {
     }
     std::vector<size_t> bad{0, 2, 1};
     if (seg_offsets_ok(bad.data(), 2)) return 7;
+    // the chunk planner at every C from 1 to total + 1
+    for (size_t C = 1; C <= o[k] - o[0] + 1; ++C)
+      if (int rc = plan_chunks(o, L, C)) return rc;
   }
+  const std::vector<size_t> empty(8, 5);  // 7 segments, all empty
+  for (size_t C : {1, 3, 7, 8})
+    if (int rc = plan_chunks(empty, 3, C)) return rc;
   printf("ok %zu\n", total);
+  return 0;
+}
+"""
+
+# SegPlanner over one offsets array at chunk knob C: the covering, the bounds, the runs, and a
+# simulation in plain integers of what the engines do with a plan (exit codes 10 ..)
+PLAN_CHUNKS = r"""
+#include <stdint.h>
+#include <vector>
+#include "segments_plan.hpp"
+using namespace msm;
+static uint64_t worth(size_t i) { return (uint64_t)i * i + 1; }
+static int plan_chunks(const std::vector<size_t> &o, size_t L, size_t chunk) {
+  const size_t k = o.size() - 1, total = o[k] - o[0];
+  const SegSizes z = seg_sizes(total, k, chunk);
+  if (z.C != std::min(std::max(total, k), chunk) || z.CP != std::min(z.C, std::max<size_t>(total, 1))) return 10;
+  if (z.pmax != z.CP + 1 || z.META != z.pmax * sizeof(SegMeta) + z.C * sizeof(uint32_t)) return 11;
+  SegPlanner pl;
+  std::vector<uint64_t> got;  // the value of every segment, in the order written
+  uint64_t carry = 0;
+  bool carried = false;
+  size_t at = o[0], seg = 0;
+  pl.begin(o.data(), k, z, L, "test");
+  while (pl.next()) {
+    // the chunks cover the points and the segments in order, without gap or overlap
+    if (pl.i != at || pl.j != seg || pl.e < pl.i || pl.je < pl.j || pl.e > o[k] || pl.je > k) return 12;
+    if (pl.cnt() == 0 && pl.nseg() == 0) return 13;  // (no progress)
+    at = pl.e, seg = pl.je;
+    const size_t np = pl.np(), nseg = pl.nseg();
+    if (nseg > z.C || pl.cnt() > z.CP || np > z.pmax) return 14;
+    if (pl.meta.size() != np || pl.src.size() != nseg || pl.npieces() + pl.pc != np) return 15;
+    if ((pl.pc != 0) != carried) return 16;  // the carried partial is there when a carry came in, and first
+    for (size_t j = pl.j; j < pl.je; ++j)
+      if (o[j + 1] > pl.e) return 17;  // a segment that is written ends in the chunk
+    if (pl.je < k && o[pl.je + 1] <= pl.e && nseg < z.C) return 18;  // and one that ends in it is written
+    // the partials: the carried one holds the value carried in, a piece sums its points
+    std::vector<uint64_t> part(np, 0);
+    size_t pt = pl.i;
+    for (size_t p = 0; p < np; ++p) {
+      const SegMeta &m = pl.meta[p];
+      if (p < pl.pc) {
+        if (m.start || m.count) return 19;
+        part[p] = carry;
+        continue;
+      }
+      if (m.count < 1 || m.count > L || pl.i + m.start != pt) return 20;  // the pieces tile [i, e)
+      for (size_t q = 0; q < m.count; ++q) part[p] += worth(pt + q);
+      pt += m.count;
+    }
+    if (pt != pl.e) return 21;
+    // the runs are contiguous: rel counts 0 .. len - 1 within each
+    size_t maxrun = 0;
+    for (size_t p = 0; p < np;) {
+      const size_t len = pl.meta[p].len;
+      if (len < 1 || p + len > np) return 22;
+      for (size_t r = 0; r < len; ++r)
+        if (pl.meta[p + r].rel != r || pl.meta[p + r].len != len) return 23;
+      maxrun = std::max(maxrun, len);
+      p += len;
+    }
+    if (maxrun != pl.maxrun) return 24;
+    // the merge of the engines: at step s the partial at rel r (a multiple of 2 s) takes in the one at r + s
+    for (size_t step = 1; step < pl.maxrun; step *= 2)
+      for (size_t p = 0; p < np; ++p) {
+        const SegMeta &m = pl.meta[p];
+        if ((m.rel & (2 * step - 1)) == 0 && m.rel + step < m.len) part[p] += part[p + step];
+      }
+    // the gather, and the next carry
+    for (size_t t = 0; t < nseg; ++t) {
+      const size_t j = pl.j + t;
+      const bool is_empty = o[j + 1] == o[j];
+      if (is_empty != (pl.src[t] == ~0u)) return 25;
+      if (!is_empty && (pl.src[t] >= np || pl.meta[pl.src[t]].rel != 0)) return 26;
+      got.push_back(is_empty ? 0 : part[pl.src[t]]);
+    }
+    carried = pl.carry();
+    if (carried != (pl.je < k && o[pl.je] < pl.e)) return 27;  // a segment is left open where points of it were summed
+    if (carried) {
+      if (pl.open_src >= np || pl.meta[pl.open_src].rel != 0) return 28;
+      carry = part[pl.open_src];
+    }
+  }
+  if (at != o[k] || seg != k || got.size() != k || carried) return 29;
+  for (size_t j = 0; j < k; ++j) {  // the direct sums
+    uint64_t want = 0;
+    for (size_t i = o[j]; i < o[j + 1]; ++i) want += worth(i);
+    if (got[j] != want) return 30;
+  }
+  // a plan that cannot fit its buffers is refused (at the first chunk that has a point)
+  SegSizes small = z;
+  small.pmax = 0, small.CP = 0;
+  pl.begin(o.data(), k, small, L, "test");
+  if (total) {
+    try {
+      while (pl.next()) {
+      }
+      return 31;
+    } catch (const std::runtime_error &err) {
+      if (std::string(err.what()) != "test: plan larger than its buffers") return 32;
+    }
+  }
   return 0;
 }
 """
@@ -284,11 +388,13 @@ int main() {
 
 def test_planner_under_sanitizers(tmp_path):
     """csrc/segments_plan.hpp in a stand-alone host program built with ASan + UBSan:
-    the edge offsets, whole and cut at every chunk size"""
+    the edge offsets, whole and cut at every chunk size, by seg_cut and by the chunk
+    planner of point_segments.hip and pairing.hip (SegPlanner), whose plans are also
+    carried out in plain integers against the direct per-segment sums"""
     if not shutil.which("g++"):
         pytest.fail("g++ missing")
     src = tmp_path / "plan_main.cpp"
-    src.write_text(PLAN_MAIN)
+    src.write_text(PLAN_CHUNKS + PLAN_MAIN)
     exe = tmp_path / "plan_main"
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-I", os.path.join(REPO, "msm_blst_amd", "csrc"), str(src), "-o", str(exe)], check=True)
