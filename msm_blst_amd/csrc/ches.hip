@@ -712,10 +712,7 @@ void Ches<G>::plan_buckets(size_t n) {
     for (int k = 1; k <= small_; ++k) w.push_back((uint32_t)B_[k]);
   if (w.size() >= (1u << 24)) throw std::runtime_error("CHES bucket space exceeds 24-bit indices");
   red_.plan(w);
-  static const int bc_env = [] {  // A/B knob: the batch reducer's level-0 chunk (0: red_'s)
-    const char *e = getenv("MSM_BATCH_L0_CHUNK");
-    return e ? std::max(0, std::min(64, atoi(e))) : 8;
-  }();
+  const int bc_env = BatchKnobs::env().batch_l0_chunk;  // the batch reducer's level-0 chunk (0: red_'s)
   if (bc_env && red_.level0_chunk() != bc_env) {
     bred_.plan(w, bc_env);
     batch_red_ = &bred_;
@@ -731,11 +728,7 @@ void Ches<G>::plan_buckets(size_t n) {
 // overrides.
 template <int G>
 int Ches<G>::batch_lanes() const {
-  static const int env = [] {
-    const char *e = getenv("MSM_BATCH_LANES");
-    return e ? std::max(1, std::min(3, atoi(e))) : 0;
-  }();
-  if (env) return env;
+  if (const int env = BatchKnobs::env().batch_lanes) return env;
   // G1 small MSMs take three lanes since round 4's single reduction group per
   // batch (2^17 / 2^18 / 2^19 batches 0.52 / 0.86 / 1.40 -> 0.49 / 0.80 / 1.35
   // ms per MSM, profiles/archive_r01_r04.txt (r04_small_lanes_ab.txt)); G2 keeps two (not measured)
@@ -952,28 +945,6 @@ float Ches<G>::time_accumulation(hipStream_t s, const uint8_t *d_scalars, size_t
 }
 
 template <int G>
-void Ches<G>::accumulate_l0(hipStream_t s, int set, int r, int bset, const void *table, int l0_bset, int gset,
-                            int slot, int l0_last) {
-  typedef typename FieldOf<G>::F F;
-  const size_t NB = bucket_count();
-  ChesFrontSet &f = fs_[set];
-  const typename WeightedReducer<G>::HeadArgs a = batch_red_->head_args(gset, slot);
-  const AccSched S = f.sort.sched(f.order.as<uint32_t>(), f.sorted.as<uint32_t>(), r, NB);
-  const AffP<F> *T = table ? static_cast<const AffP<F> *>(table) : table_.as<AffP<F>>();
-  // lanes: one per bucket / output (G1), two (G2 lane pairs)
-  const unsigned l0b = (unsigned)((G * a.nout + 255) / 256), accb = (unsigned)((G * NB + 255) / 256);
-  if constexpr (G == 1)
-    hipLaunchKernelGGL((k_accumulate_l0<AffP<F>>), dim3(accb + l0b), dim3(256), 0, s, S, T,
-                       buckets_[bset].as<Xyzz<F>>(), NB, buckets_[l0_bset].as<Xyzz<F>>(), a.idx, a.starts,
-                       static_cast<Xyzz<F> *>(a.dst), a.nout, l0b, l0_last);
-  else
-    hipLaunchKernelGGL((k_accumulate2p_l0<AffP<F>>), dim3(accb + l0b), dim3(256), 0, s, S, T,
-                       buckets_[bset].as<Xyzz<F>>(), NB, buckets_[l0_bset].as<Xyzz<F>>(), a.idx, a.starts,
-                       static_cast<Xyzz<F> *>(a.dst), a.nout, l0b, l0_last);
-  MSM_HIP_CHECK(hipGetLastError());
-}
-
-template <int G>
 void Ches<G>::run(hipStream_t s, const uint8_t *d_scalars, size_t stride, hfp::Jac<HF> *out) {
   DeviceGuard g(dev_);
   if (stride < 32) throw std::runtime_error("CHES scalars must be 32-byte strings");
@@ -1009,6 +980,187 @@ void Ches<G>::run(hipStream_t s, const uint8_t *d_scalars, size_t stride, hfp::J
   }
 }
 
+// The batch (run_jobs): plan, sink and issue loops in batch_plan.hpp, DESIGN 29.
+
+// every operation of the issue loops as the one HIP call or launch it stands for
+template <int G>
+struct Ches<G>::BatchSink {
+  Ches &e;
+  const BatchPlan &p;
+  WeightedReducer<G> &red;
+  hipStream_t st[kBatchStreams];
+  const uint8_t *scalars;
+  size_t stride, set_stride;
+  const void *const *tables;
+  // where the groups' window sums land: the pinned read-back slots, or the
+  // caller's device exchange buffer (dev_out: ChesMulti gathers it over RCCL
+  // and combines on the host; the host combine is then skipped)
+  uint8_t *out_base;
+  bool prof;
+  std::vector<size_t> prof_k;  // profiling: acc_ev_ pairs recorded (per MSM, or per accumulation group)
+
+  hipEvent_t ev(size_t i) const { return i < p.events ? e.bev_[i] : e.ev_tail_[i - p.events]; }
+  const uint8_t *job_scalars(size_t k) const {
+    return scalars + (k / p.nseg) * set_stride + (k % p.nseg) * e.n_ * stride;
+  }
+  const void *job_table(size_t k) const { return tables[k % p.nseg]; }
+  uint8_t *slots(size_t g) const { return e.scal_.template as<uint8_t>() + (g % p.nsg) * p.fg_max * p.sslot; }
+
+  void wait(int s, size_t i) { MSM_HIP_CHECK(hipStreamWaitEvent(st[s], ev(i), 0)); }
+  void record(size_t i, int s) { MSM_HIP_CHECK(hipEventRecord(ev(i), st[s])); }
+  void host_wait(size_t i) { MSM_HIP_CHECK(hipEventSynchronize(ev(i))); }
+  void sync(int s) { MSM_HIP_CHECK(hipStreamSynchronize(st[s])); }
+  void copy_set(size_t g, size_t k) {
+    MSM_HIP_CHECK(hipMemcpyAsync(slots(g) + (k - p.fgb[g]) * p.sslot, job_scalars(k), p.sslot, hipMemcpyHostToDevice,
+                                 st[kCopy]));
+  }
+  void front(size_t g) {
+    e.digits_sort(st[kFront], p.host ? slots(g) : job_scalars(p.fgb[g]), stride, p.host ? p.sslot : p.jstride,
+                  (int)(p.fgb[g + 1] - p.fgb[g]), (int)(g % p.nfr), p.fine_bt);
+  }
+  void accumulate(int s, size_t g, size_t k, int bset) {
+    e.accumulate(st[s], (int)(g % p.nfr), (int)(k - p.fgb[g]), bset, job_table(k));
+  }
+  void accumulate_group(int s, size_t g, int gb) {
+    e.accumulate_sets(st[s], (int)(g % p.nfr), (int)(p.fgb[g + 1] - p.fgb[g]), gb, job_table(p.fgb[g]));
+  }
+  void level0(int s, int bset, int rset, int slot) { red.launch_head_slot(st[s], e.buckets_[bset].p, rset, slot); }
+  void level0_group(int s, int gb, size_t off, int rset, int slot0, int m) {
+    const size_t NB = e.bucket_count();
+    red.launch_head_slots(st[s], e.gbuckets_[gb].template as<uint8_t>() + off * NB * sizeof(Xyzz<typename FieldOf<G>::F>),
+                          NB, rset, slot0, m);
+  }
+  // the dense stage into the read-back slots, or (the last group, bit_tail) the bit phase into host_bits_
+  void tail(int s, int rset, size_t first, size_t m, bool last) {
+    if (p.bit_tail && last) {
+      red.launch_tail_group_bits(st[s], rset, (int)m, p.tail_coop);
+      red.copy_out_group_bits(st[s], rset, (int)m, e.host_bits_);
+    } else {
+      red.launch_tail_group(st[s], rset, (int)m, p.tail_coop && last);
+      red.copy_out_group(st[s], rset, (int)m, out_base + first * red.out_bytes());
+    }
+  }
+  void combine(size_t, size_t) {}
+  void prof_begin(int s, size_t k) {
+    if (prof) MSM_HIP_CHECK(hipEventRecord(e.acc_ev_[2 * k], st[s]));
+  }
+  void prof_end(int s, size_t k) {
+    if (!prof) return;
+    MSM_HIP_CHECK(hipEventRecord(e.acc_ev_[2 * k + 1], st[s]));
+    prof_k.push_back(k);
+  }
+};
+
+// The batch's own streams, created at the first batch.  Fronts at the greatest
+// priority: their short memory-bound kernels take the first CU slots an
+// accumulation releases (the next accumulation waits for them); the reductions
+// at normal priority, beside the accumulations (the same priority for both
+// measured equal, tools/batch_sched.py).
+template <int G>
+void Ches<G>::batch_streams() {
+  if (fstream_) return;
+  int least = 0, greatest = 0;
+  MSM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  MSM_HIP_CHECK(hipStreamCreateWithPriority(&fstream_, hipStreamNonBlocking, greatest));
+  for (int t = 0; t < kBSets; ++t) {
+    MSM_HIP_CHECK(hipStreamCreateWithPriority(&tails_[t], hipStreamNonBlocking, 0));
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_tail_[t], hipEventDisableTiming));
+  }
+  MSM_HIP_CHECK(hipStreamCreateWithFlags(&cstream_, hipStreamNonBlocking));
+  // a stream's hardware queue is set up at its first launch: do that here,
+  // not inside the first batch that happens to use the stream
+  prime_.ensure(256);
+  for (hipStream_t q : {fstream_, tails_[0], tails_[1], cstream_}) MSM_HIP_CHECK(hipMemsetAsync(prime_.p, 0, 256, q));
+  for (hipStream_t q : {fstream_, tails_[0], tails_[1], cstream_}) MSM_HIP_CHECK(hipStreamSynchronize(q));
+}
+
+template <int G>
+BatchPlan Ches<G>::batch_plan(size_t nsets, size_t nseg, size_t stride, size_t set_stride, bool scalars_on_host,
+                              bool dev_out) const {
+  BatchShape z;
+  z.nsets = nsets, z.nseg = nseg, z.n = n_, z.stride = stride, z.set_stride = set_stride, z.h = p_.h;
+  z.buckets = bucket_count(), z.lanes = batch_lanes(), z.group = G;
+  z.host = scalars_on_host, z.dev_out = dev_out, z.bit_tail_ok = batch_red_->has_bit_tail();
+  z.bucket_bytes = sizeof(Xyzz<typename FieldOf<G>::F>);
+  z.out_bytes = batch_red_->out_bytes(), z.bit_bytes = batch_red_->bit_bytes();
+  return BatchPlan::ches(z, BatchKnobs::env());
+}
+
+static void ensure_pinned(void *&buf, size_t &have, size_t need, size_t alloc) {
+  if (have >= need) return;
+  if (buf) (void)hipHostFree(buf);
+  buf = nullptr;
+  have = 0;
+  MSM_HIP_CHECK(hipHostMalloc(&buf, alloc, hipHostMallocDefault));
+  have = alloc;
+}
+
+// every buffer and event the issue loops touch exists before the first launch
+template <int G>
+void Ches<G>::batch_buffers(const BatchPlan &p, hipStream_t s, size_t stride) {
+  ensure_pinned(host_out_, host_out_bytes_, p.out_need, p.out_alloc);
+  ensure_pinned(host_bits_, host_bits_bytes_, p.bits_need, p.bits_alloc);
+  for (int b = 0; b < p.bucket_sets; ++b) (p.sched == kAccGroups ? gbuckets_ : buckets_)[b].ensure(p.bucket_set_bytes);
+  if ((int)fs_.size() < p.nfr) fs_.resize(p.nfr);
+  for (int t = 0; t < p.nred; ++t) batch_red_->ensure_group(t, (int)p.group_max);
+  // front sets sized for a whole front group (the sort's scan scratch too): run
+  // one sort of fg_max sets per set before the loop if they are not yet sized
+  // (fg_max dummy sets of all-zero scalars, outside the batch timing)
+  bool unsized = false;
+  for (int f = 0; f < p.nfr; ++f) unsized |= fs_[f].sorted.bytes < p.sorted_min;
+  scal_.ensure(p.scal_bytes);
+  if (unsized) scal_.ensure(p.scal_dummy_bytes);
+  for (int f = 0; f < p.nfr; ++f)
+    if (fs_[f].sorted.bytes < p.sorted_min) {
+      MSM_HIP_CHECK(hipMemsetAsync(scal_.p, 0, p.fg_max * p.sslot, s));
+      digits_sort(s, scal_.as<uint8_t>(), stride, p.sslot, (int)p.fg_max, f);
+      MSM_HIP_CHECK(hipStreamSynchronize(s));
+    }
+  while (profile_ && acc_ev_.size() < std::max<size_t>(2 * p.count, 2 * 64)) {
+    hipEvent_t e;
+    MSM_HIP_CHECK(hipEventCreate(&e));
+    acc_ev_.push_back(e);
+  }
+  while (bev_.size() < std::max(p.events, p.events_floor)) {
+    hipEvent_t e;
+    MSM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    bev_.push_back(e);
+  }
+}
+
+// the per-MSM host Horner (~20 us each) over the host worker threads (with one
+// reduction group per batch every combine runs after the last tail), and the
+// profiling read-out: accumulation time per MSM over the batch
+template <int G>
+void Ches<G>::batch_finish(const BatchPlan &p, const std::vector<size_t> &prof_k, hfp::Jac<HF> *outs, bool dev_out,
+                           bool prof) {
+  WeightedReducer<G> &red = *batch_red_;
+  const size_t ob = red.out_bytes(), bb = red.bit_bytes();
+  const size_t last_first = p.rg.first(p.rg.groups() - 1);  // the last group's MSMs: host_bits_ when bit_tail
+  auto combine_k = [&](size_t k) {
+    outs[k] = p.bit_tail && k >= last_first ? red.combine_bits((const uint8_t *)host_bits_ + (k - last_first) * bb)
+                                            : red.combine((const uint8_t *)host_out_ + k * ob)[0];
+  };
+  if (dev_out) {
+    // the window sums stay in dev_out for the caller's exchange
+  } else if (p.count >= 4) {
+    WorkerPool::get().parallel_for(p.count, combine_k);
+  } else {
+    for (size_t k = 0; k < p.count; ++k) combine_k(k);
+  }
+  if (!prof) return;
+  float sum = 0;
+  for (size_t k : prof_k) {
+    float ms;
+    MSM_HIP_CHECK(hipEventSynchronize(acc_ev_[2 * k + 1]));
+    MSM_HIP_CHECK(hipEventElapsedTime(&ms, acc_ev_[2 * k], acc_ev_[2 * k + 1]));
+    sum += ms;
+  }
+  times_ = PhaseTimes();
+  times_.accumulate = sum / (float)p.count;
+  times_.accumulate_launches = (int)prof_k.size();
+}
+
 template <int G>
 void Ches<G>::run_jobs(hipStream_t s, const uint8_t *scalars, size_t stride, size_t set_stride, size_t nsets,
                        size_t nseg, const void *const *tables, hfp::Jac<HF> *outs, bool scalars_on_host,
@@ -1016,584 +1168,22 @@ void Ches<G>::run_jobs(hipStream_t s, const uint8_t *scalars, size_t stride, siz
   DeviceGuard g(dev_);
   if (stride < 32) throw std::runtime_error("CHES scalars must be 32-byte strings");
   if (nseg < 1) throw std::runtime_error("run_jobs: no segments");
-  WeightedReducer<G> &red = *batch_red_;
-  // the dense stage of the batch's LAST group runs its adds over 4 waves each
-  // (nothing else left to overlap; MSM_TAIL_COOP=0: one lane per add throughout)
-  static const bool tail_coop = [] {
-    const char *e = getenv("MSM_TAIL_COOP");
-    return !e || atoi(e) != 0;
-  }();
-  // jobs k = set (k / nseg), segment (k % nseg); every loop below runs over jobs
-  const size_t count = nsets * nseg;
-  if (count == 0) return;
+  if (nsets * nseg == 0) return;
   if (n_ == 0) {
-    std::memset(outs, 0, sizeof(*outs) * count);
+    std::memset(outs, 0, sizeof(*outs) * nsets * nseg);
     return;
   }
-  auto job_scalars = [&](size_t k) { return scalars + (k / nseg) * set_stride + (k % nseg) * n_ * stride; };
-  auto job_table = [&](size_t k) { return tables[k % nseg]; };
-  // a front group of several jobs reads their scalars with one stride: the
-  // segments' slices are n strings apart, so groups > 1 need packed sets
-  const size_t jstride = nseg == 1 ? set_stride : n_ * stride;
-  const bool packed = nseg == 1 || set_stride == nseg * n_ * stride;
-  if (!fstream_) {
-    // fronts at the greatest priority: their short memory-bound kernels take the
-    // first CU slots an accumulation releases (the next accumulation waits for
-    // them); the reductions at normal priority, beside the accumulations (the
-    // same priority for both measured equal, tools/batch_sched.py)
-    int least = 0, greatest = 0;
-    MSM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    static const int front_prio = [] {  // A/B knob: 1 greatest (default), 0 normal, -1 least
-      const char *e = getenv("MSM_FRONT_PRIO");
-      return e ? atoi(e) : 1;
-    }();
-    MSM_HIP_CHECK(hipStreamCreateWithPriority(&fstream_, hipStreamNonBlocking,
-                                              front_prio > 0 ? greatest : front_prio < 0 ? least : 0));
-    static const bool tail_hi = [] {  // A/B knob: reduction streams at the front's (greatest) priority
-      const char *e = getenv("MSM_TAIL_PRIO");
-      return e && atoi(e) != 0;
-    }();
-    for (int t = 0; t < kBSets; ++t) {
-      MSM_HIP_CHECK(hipStreamCreateWithPriority(&tails_[t], hipStreamNonBlocking, tail_hi ? greatest : 0));
-      MSM_HIP_CHECK(hipEventCreateWithFlags(&ev_tail_[t], hipEventDisableTiming));
-    }
-    MSM_HIP_CHECK(hipStreamCreateWithFlags(&cstream_, hipStreamNonBlocking));
-    // a stream's hardware queue is set up at its first launch: do that here,
-    // not inside the first batch that happens to use the stream
-    prime_.ensure(256);
-    for (hipStream_t q : {fstream_, tails_[0], tails_[1], cstream_}) MSM_HIP_CHECK(hipMemsetAsync(prime_.p, 0, 256, q));
-    for (hipStream_t q : {fstream_, tails_[0], tails_[1], cstream_}) MSM_HIP_CHECK(hipStreamSynchronize(q));
-  }
-  // one pinned read-back slot per MSM of the batch: the host never waits inside
-  // the issue loop, so MSM k+1's front is queued while MSM k still accumulates
-  const size_t ob = red.out_bytes();  // a group's read-back lands contiguously
-  // reduction groups of <= kGroup MSMs (balanced sizes), alternating between
-  // the reducer sets / tail streams.  MSM_LAST_GROUP=m (A/B knob): the batch's
-  // last m MSMs form a group of their own, so the earlier group's tail runs
-  // beside the last accumulations and only a narrow tail follows the last one
-  static const size_t group_max = [] {  // A/B knob: MSMs per reduction group (default kGroup)
-    const char *e = getenv("MSM_RED_GROUP");
-    return (size_t)(e ? std::max(1, std::min(32, atoi(e))) : kGroup);
-  }();
-  static const size_t last_env = [] {
-    const char *e = getenv("MSM_LAST_GROUP");
-    return (size_t)(e ? std::max(0, std::min(32, atoi(e))) : 0);
-  }();
-  std::vector<size_t> gfirst;  // group q holds MSMs [gfirst[q], gfirst[q + 1])
-  {
-    const size_t last = last_env && count > last_env ? std::min(last_env, group_max) : 0, nmain = count - last;
-    const size_t ng = (nmain + group_max - 1) / group_max, Rm = (nmain + ng - 1) / ng;
-    for (size_t k = 0; k < nmain; k += Rm) gfirst.push_back(k);
-    if (last) gfirst.push_back(nmain);
-    gfirst.push_back(count);
-  }
-  const size_t ngroups = gfirst.size() - 1;
-  std::vector<uint32_t> gof(count);
-  for (size_t q = 0; q < ngroups; ++q)
-    for (size_t k = gfirst[q]; k < gfirst[q + 1]; ++k) gof[k] = (uint32_t)q;
-  auto grp = [&](size_t k) { return (size_t)gof[k]; };              // the reduction group of MSM k
-  auto gslot = [&](size_t k) { return k - gfirst[gof[k]]; };        // its slot in the group
-  auto gend = [&](size_t k) { return k + 1 == gfirst[gof[k] + 1]; };  // the group's last MSM
-  if (host_out_bytes_ < count * ob) {  // at least 256 MSMs' worth (a few hundred KiB): no regrowth per batch size
-    if (host_out_) (void)hipHostFree(host_out_);
-    host_out_ = nullptr;
-    host_out_bytes_ = 0;
-    const size_t bytes = std::max<size_t>(count, 256) * ob;
-    MSM_HIP_CHECK(hipHostMalloc(&host_out_, bytes, hipHostMallocDefault));
-    host_out_bytes_ = bytes;
-  }
-  // where the groups' window sums land: the pinned read-back slots, or the
-  // caller's device exchange buffer (dev_out: ChesMulti gathers it over RCCL
-  // and combines on the host; the combine below is then skipped)
-  uint8_t *const out_base = dev_out ? static_cast<uint8_t *>(dev_out) : static_cast<uint8_t *>(host_out_);
-  // The batch's LAST reduction group ends in bit sums (launch_tail_group_bits):
-  // its tail runs after the last accumulation with the chip otherwise idle, and
-  // the bit phase is ~10 latency-bound levels instead of the dense stage's 2 s
-  // (profiles/r06_small_trace.txt).  Earlier groups keep the dense stage: their
-  // tails run beside accumulations, where the 2 s-Jacobian read-backs cost
-  // (DESIGN 5).  MSM_BIT_TAIL=0: dense stage for every group.
-  static const bool bit_tail_env = [] {
-    const char *e = getenv("MSM_BIT_TAIL");
-    return !e || atoi(e) != 0;
-  }();
-  const bool bit_tail = bit_tail_env && !dev_out && red.has_bit_tail();
-  const size_t bb = red.bit_bytes();
-  if (bit_tail && host_bits_bytes_ < (size_t)group_max * bb) {
-    if (host_bits_) (void)hipHostFree(host_bits_);
-    host_bits_ = nullptr;
-    host_bits_bytes_ = 0;
-    const size_t bytes = (size_t)std::max<size_t>(group_max, 32) * bb;
-    MSM_HIP_CHECK(hipHostMalloc(&host_bits_, bytes, hipHostMallocDefault));
-    host_bits_bytes_ = bytes;
-  }
-  // a group's tail + read-back: the dense stage into the read-back slots, or
-  // (the last group, bit_tail) the bit phase into host_bits_
-  auto group_tail = [&](hipStream_t ts, int rset, size_t first, size_t nmsm, bool last_group) {
-    if (bit_tail && last_group) {
-      red.launch_tail_group_bits(ts, rset, (int)nmsm, tail_coop);
-      red.copy_out_group_bits(ts, rset, (int)nmsm, host_bits_);
-    } else {
-      red.launch_tail_group(ts, rset, (int)nmsm, tail_coop && last_group);
-      red.copy_out_group(ts, rset, (int)nmsm, out_base + first * ob);
-    }
-  };
-  // (group size cap: kFrontGroupDefault, or MSM_FRONT_GROUP=<1..8>; engine.hpp)
-  // (small MSMs on lanes: groups of 2 on two lanes -- half the front launches,
-  // measured 0.551 -> 0.530 ms per 2^17 MSM and 0.874 -> 0.845 at 2^18 -- and 4
-  // on three lanes (profiles/archive_r01_r04.txt (r04_small_lanes_ab.txt)); the 2^20 batch keeps 1,
-  // its wider fronts starve the accumulation, r03_front_group_ab.txt and
-  // r04_front_group_ab.txt)
-  static const size_t fg_env = [] {
-    const char *e = getenv("MSM_FRONT_GROUP");
-    return e ? (size_t)std::min(kFrontGroup, std::max(1, atoi(e))) : (size_t)0;
-  }();
-  const int nl = batch_lanes();
-  // the batch fronts' fine-pass workgroup (bucket_sort.hpp k_bs_fine): 1024
-  // threads; MSM_FINE_BT=256 selects the variant that fits beside three
-  // accumulation waves per SIMD -- measured slower (H2D 408-411 vs 415-420 M,
-  // resident 423-429 vs 434-440 M pairs/s, profiles/archive_r01_r04.txt (r04_fine_bt_ab.txt))
-  static const int fine_bt = [] {
-    const char *e = getenv("MSM_FINE_BT");
-    return e && atoi(e) == 256 ? 256 : 1024;
-  }();
-  static const bool acc_group_env = [] {  // accumulation groups (below); MSM_ACC_GROUP=0: per-MSM lanes
-    const char *e = getenv("MSM_ACC_GROUP");
-    return !e || atoi(e) != 0;
-  }();
-  const bool acc_groups = nl >= 2 && nseg == 1 && acc_group_env;
-  // (one lane, the 2^20 headline: one accumulation launch per MSM.  Alone, two
-  // 2^20 sets in one grid accumulate in 1.70 ms per set vs 1.96 for one
-  // (profiles/r05_acc_rate.txt: a launch's last waves leave the chip half
-  // idle), but in the batch the front and level 0 beside it fill that tail:
-  // groups of 2 per launch measured 427 vs 431-433 M pairs/s with H2D, the
-  // in-batch accumulation 1.75-1.80 vs 1.72-1.77 ms per set, profiles/r05_head_front_group_ab.txt)
-  const size_t fg_max = !packed ? 1 : fg_env ? fg_env : acc_groups ? 4 : nl >= 3 ? 4 : nl == 2 ? 2 : (size_t)kFrontGroupDefault;
-  // front groups of 1, 1, 2, 4, then fg_max MSMs: the first accumulation
-  // starts after one front, and each group's host sets (copied while the earlier
-  // groups accumulate: a set copies in ~0.6 ms, an MSM accumulates in ~2.3) are
-  // in HBM before its front is due -- a first group of eight stalled the H2D
-  // batch by ~5 ms (the 256-MiB copy, then the front, before MSM 1).
-  const std::vector<size_t> fgb = front_groups(count, fg_max);
-  const size_t nfg = fgb.size() - 1;
-  // every buffer the loop touches exists before the first launch (an allocation
-  // inside the issue loop could synchronise the device)
-  const size_t NB = bucket_count(), n = n_;
-  if (acc_groups)
-    for (DevBuf &b : gbuckets_) b.ensure(fg_max * NB * sizeof(Xyzz<typename FieldOf<G>::F>));
-  else
-    for (int b = 0; b < std::max(kBSets, nl); ++b) buckets_[b].ensure(NB * sizeof(Xyzz<typename FieldOf<G>::F>));
-  // sized for kGroup whatever this batch's R: a later, larger batch must not
-  // reallocate (a hipFree inside the pipelined region would synchronise it)
-  // (both reducer sets, and both bucket sets, whatever this batch's length: a
-  // short warm-up batch must leave nothing to allocate inside a longer one)
-  // front sets and reducer sets in rotation: the lane schedule (small MSMs,
-  // periods of a few hundred us) keeps fronts further ahead and lets group q
-  // reuse reducer set q % 4 after tail q - 4 (a tail is ~30 latency-bound
-  // launches, ~1 ms beside the accumulations: with 2 sets group q + 2 waited
-  // for it, profiles/archive_r01_r04.txt (r04_batch_trace_2p17.txt))
-  // Front phase (small-MSM accumulation groups; MSM_FRONT_PHASE=1 enables):
-  // one front set per front group, up to kFrontPhase (capped at ~4 GiB of
-  // front sets), and the first accumulation waits for every front of that
-  // phase.  Fronts beside accumulations starve (their 1024-thread fine-pass
-  // workgroups wait for a whole CU to drain: 1.1-1.6 ms instead of 34 us in the
-  // 2^17 trace, profiles/r05_small_trace.txt); run first, on the whole chip,
-  // the batch's fronts take ~60 us per set and the accumulations then run
-  // without them.
-  // measured slower, so off by default: 2^17 shard 0.461 vs 0.438 ms per MSM,
-  // 2^16 plain 0.385 vs 0.368 (profiles/r05_shard_pip_study.txt)
-  static const bool phase_env = [] {
-    const char *e = getenv("MSM_FRONT_PHASE");
-    return e && atoi(e) != 0;
-  }();
-  const bool phase = acc_groups && phase_env;
-  const size_t fs_bytes = fg_max * n * (size_t)p_.h * 16 + 1;  // ~ one front set (sorted, ranks, interleave)
-  const int nfr = phase ? (int)std::max<size_t>(kFrontsMax, std::min<size_t>(kFrontPhase, ((size_t)4 << 30) / fs_bytes))
-                        : nl >= 2 ? kFrontsMax : kFronts;
-  const int nred = nl >= 2 ? 4 : 2;
-  if ((int)fs_.size() < nfr) fs_.resize(nfr);
-  for (int t = 0; t < nred; ++t) red.ensure_group(t, (int)group_max);
-  // front sets sized for a whole front group (the sort's scan scratch too): run
-  // one sort of fg_max sets per set before the loop if they are not yet sized
-  // (fg_max dummy sets of all-zero scalars, outside the batch timing)
-  const size_t sslot = n * stride;  // one device scalar slot
-  bool unsized = false;
-  for (int f = 0; f < nfr; ++f) unsized |= fs_[f].sorted.bytes < n * (size_t)p_.h * fg_max * 4;
-  // host sets: device slots for up to 32 front groups (<= 2 GiB, at least 4),
-  // so a batch of up to 32 groups issues every copy at its start and the copy
-  // stream runs them back to back, ahead of the fronts; a longer batch copies
-  // group g once group g - nsg's front has consumed its slots.  With 4 slots
-  // (copies issued 4 MSMs ahead, each after a front event) the 2^20 H2D
-  // headline fell into a slow schedule in about half the runs (372-391 vs
-  // 411-417 M pairs/s, more often after a 3-set warm-up); with a slot per set
-  // every run gave 418-423 M (profiles/archive_r01_r04.txt (r04_h2d_slots_ab.txt))
-  static const size_t nsg_env = [] {
-    const char *e = getenv("MSM_H2D_SLOTS");  // A/B knob: slot groups (copies issued that far ahead)
-    return (size_t)(e ? std::max(2, std::min(256, atoi(e))) : 0);
-  }();
-  const size_t slot_groups =
-      std::max<size_t>(nsg_env ? nsg_env : std::max<size_t>(4, std::min<size_t>(32, ((size_t)2 << 30) / (fg_max * sslot))),
-                       (size_t)nfr - 1);
-  // (every group's copies are enqueued before its front: nsg >= nfr - 1)
-  const size_t nsg = std::max<size_t>(std::min(slot_groups, nfg), (size_t)nfr - 1);
-  // sized for slot_groups whatever this batch's length: a later, longer batch
-  // must not reallocate inside its pipelined region
-  if (scalars_on_host) scal_.ensure(slot_groups * fg_max * sslot + 16);
-  if (unsized) scal_.ensure(fg_max * sslot + 16);
-  for (int f = 0; f < nfr; ++f)
-    if (fs_[f].sorted.bytes < n * (size_t)p_.h * fg_max * 4) {
-      MSM_HIP_CHECK(hipMemsetAsync(scal_.p, 0, fg_max * sslot, s));
-      digits_sort(s, scal_.as<uint8_t>(), stride, sslot, (int)fg_max, f);
-      MSM_HIP_CHECK(hipStreamSynchronize(s));
-    }
+  batch_streams();
+  const BatchPlan p = batch_plan(nsets, nseg, stride, set_stride, scalars_on_host, dev_out != nullptr);
+  batch_buffers(p, s, stride);
   const bool prof = profile_;
   profile_ = false;
-  if (prof)
-    while (acc_ev_.size() < std::max<size_t>(2 * count, 2 * 64)) {
-      hipEvent_t e;
-      MSM_HIP_CHECK(hipEventCreate(&e));
-      acc_ev_.push_back(e);
-    }
-  // Streams, front groups g (front set g % nfr), bucket sets k % kBSets and,
-  // for host scalars, nsg groups of device scalar slots (g % nsg):
-  //   fstream_:  digits + sort of front group g: ONE pass per stage over its R_g
-  //              scalar sets (bucket_sort.hpp), after group g - 3's accumulations
-  //              released the front set.  Issued when group g - 2's accumulations
-  //              are enqueued, so it runs beside them or g - 1's; at the greatest priority,
-  //              its short memory-bound kernels take the CU slots the
-  //              accumulation's retiring workgroups free;
-  //   s:         accumulation k into bucket set k % kBSets (after MSM k-2's
-  //              reduction head released it) -- back to back, the VALU-bound
-  //              critical path;
-  //   tails_[t]: the reductions of reduction group q = k / R, t = q % 2: level 0
-  //              of each MSM into its slot of reducer set t right after its
-  //              accumulation, then, after the group's last MSM, ONE launch per
-  //              tail level for the whole group and one read-back.  Every launch
-  //              that runs beside an accumulation costs it ~10-20 us
-  //              (profiles/archive_r01_r04.txt (r02_batch_sched2.txt)), so the ~35 latency-bound levels
-  //              are paid once per group, not once per MSM.  Two streams: group
-  //              q+1's level 0s never queue behind group q's tail;
-  //   cstream_:  host scalars: the H2D copies of front group g's sets into slot
-  //              group g % nsg, after front g - nsg consumed it, on their own stream.
-  // No host waits inside the loop: every MSM has its own pinned read-back slot.
-  // Reducer set t is reused by group q + 2 only after group q's tail: both are
-  // in order on tails_[t].
-  // dependency events for at least 64 MSMs, created once (not inside a timed batch)
-  while (bev_.size() < std::max<size_t>(3 * count + 2 * nfg + ngroups + 1, 3 * 64 + 3 * 64 + 1)) {
-    hipEvent_t e;
-    MSM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    bev_.push_back(e);
-  }
-  hipEvent_t *eva = bev_.data() + 1, *evh = eva + count, *evf = evh + count, *evc = evf + nfg, *evt = evc + nfg;
-  std::vector<size_t> prof_k;  // profiling: acc_ev_ pairs recorded (per MSM, or per accumulation group)
-  MSM_HIP_CHECK(hipEventRecord(bev_[0], s));  // the batch starts after prior work on s
-  MSM_HIP_CHECK(hipStreamWaitEvent(fstream_, bev_[0], 0));
-  // The copy stream does NOT wait on the batch-start event: an SDMA copy
-  // enqueued behind a cross-stream event wait now and then blocked the issuing
-  // thread -- the one that enqueues the whole pipeline -- for 7-9 ms (rocprofv3
-  // HIP API traces of bench.py: the batch's second hipMemcpyAsync took 7.4 ms in
-  // 3 of 5 traced runs, the GPU idle meanwhile; tools/microbench/copy_block.hip:
-  // blocked calls only with the wait; profiles/r05_h2d_block.txt).  Prior work
-  // on the caller's stream (which may write the host sets) is awaited on the
-  // host instead; the device slots are only read by this engine's batches,
-  // which end synchronised.
-  if (scalars_on_host) MSM_HIP_CHECK(hipEventSynchronize(bev_[0]));
-  for (int t = 0; t < kBSets; ++t) MSM_HIP_CHECK(hipStreamWaitEvent(tails_[t], bev_[0], 0));
-  auto slots = [&](size_t g) { return scal_.as<uint8_t>() + (g % nsg) * fg_max * sslot; };
-  // MSM_ZERO_COPY_SCALARS=1 (A/B knob): page-locked host sets are read by the
-  // digit kernel straight over PCIe instead of being copied by SDMA first
-  static const bool zc_env = [] {
-    const char *e = getenv("MSM_ZERO_COPY_SCALARS");
-    return e && atoi(e) != 0;
-  }();
-  bool zero_copy = false;
-  if (scalars_on_host && zc_env) {
-    hipPointerAttribute_t a;
-    zero_copy = hipPointerGetAttributes(&a, scalars) == hipSuccess && a.type == hipMemoryTypeHost;
-    if (!zero_copy) (void)hipGetLastError();
-  }
-  auto copy_group = [&](size_t g) {
-    if (!scalars_on_host || zero_copy || g >= nfg) return;
-    if (g >= nsg) MSM_HIP_CHECK(hipStreamWaitEvent(cstream_, evf[g - nsg], 0));  // slots consumed by front g - nsg
-    for (size_t k = fgb[g]; k < fgb[g + 1]; ++k)
-      MSM_HIP_CHECK(hipMemcpyAsync(slots(g) + (k - fgb[g]) * sslot, job_scalars(k), sslot, hipMemcpyHostToDevice,
-                                   cstream_));
-    MSM_HIP_CHECK(hipEventRecord(evc[g], cstream_));
-  };
-  static const bool front_after_l0 = [] {
-    const char *e = getenv("MSM_FRONT_AFTER_L0");
-    return e && atoi(e) != 0;
-  }();
-  // Paced copies (MSM_COPY_PACE=L, default 8; 0 or < 3: all at the batch
-  // start): the first L front groups' sets are copied at the batch start, the
-  // copy of group g >= L is issued when the accumulation L MSMs before it has
-  // finished (a host wait on its event -- no cross-stream wait on the copy
-  // stream), so later copies run one per period beside one MSM instead of back
-  // to back beside the first five: 2^20 H2D 436.4 / 439.2 / 439.9 vs 432.4 /
-  // 436.2 / 436.7 M pairs/s (L = 8 vs all at the start, tools/h2d_ab.py
-  // medians, alternating on one box; profiles/r05_copy_pace_ab.txt).  The wait
-  // targets MSM fgb[g] - L clamped to the last accumulation already enqueued in
-  // THIS batch (acc_enq; in the accumulation-group schedule front g is issued
-  // when only the groups up to g - nfr + 1 are enqueued), so it
-  // never waits on a stale or unrecorded event and cannot deadlock.
-  static const size_t pace_env = [] {
-    const char *e = getenv("MSM_COPY_PACE");
-    return (size_t)(e ? std::max(0, std::min(32, atoi(e))) : 8);
-  }();
-  const size_t pace = scalars_on_host && !zero_copy && pace_env >= 3 ? pace_env : 0;
-  size_t acc_enq = 0;  // accumulations whose eva[] event is recorded in this batch
-  auto front_group = [&](size_t g) {
-    if (g >= nfg) return;
-    const bool copied = scalars_on_host && !zero_copy;
-    if (pace && g >= pace && g < nsg) {
-      if (acc_enq) MSM_HIP_CHECK(hipEventSynchronize(eva[std::min(fgb[g] - pace, acc_enq - 1)]));
-      copy_group(g);
-    }
-    if (copied) MSM_HIP_CHECK(hipStreamWaitEvent(fstream_, evc[g], 0));
-    if (g >= (size_t)nfr) {  // front set g % nfr: every accumulation of group g - nfr has read it
-      const size_t last = fgb[g - nfr + 1] - 1;
-      MSM_HIP_CHECK(hipStreamWaitEvent(fstream_, eva[last], 0));
-      // A/B knob: also after that MSM's level 0, so the front starts beside the
-      // next accumulation instead of beside level 0 (one-lane schedule);
-      // measured no better (profiles/archive_r01_r04.txt (r04_h2d_slots_ab.txt), call 19)
-      if (front_after_l0 && nl < 2) MSM_HIP_CHECK(hipStreamWaitEvent(fstream_, evh[last], 0));
-      for (size_t d = 1; d < (size_t)nl && last >= d && last - d >= fgb[g - nfr]; ++d)  // its other lanes
-        MSM_HIP_CHECK(hipStreamWaitEvent(fstream_, eva[last - d], 0));
-    }
-    const uint8_t *src = copied ? slots(g) : job_scalars(fgb[g]);
-    digits_sort(fstream_, src, stride, copied ? sslot : jstride, (int)(fgb[g + 1] - fgb[g]), (int)(g % nfr),
-                fine_bt);
-    MSM_HIP_CHECK(hipEventRecord(evf[g], fstream_));
-  };
-  for (size_t g = 0; g < (pace ? std::min(nsg, pace) : nsg); ++g) copy_group(g);
-  // Accumulation k waits for level 0 of MSM k - 1, so level 0 runs beside the
-  // fronts, never beside the next accumulation.  Without this wait the batch
-  // fell, in about one run in three, into a schedule where fronts ran two MSMs
-  // ahead and every accumulation started at once beside the previous level 0:
-  // level 0 then took 0.5-1.2 ms instead of 0.41, the accumulations 2.2-2.7 ms
-  // instead of 1.8, and the H2D headline 342-386 M pairs/s instead of ~420
-  // (kernel traces, profiles/archive_r01_r04.txt (r03_spread_trace.txt)); with it 19 of 19 runs on
-  // three boxes gave 410-422 M (profiles/archive_r01_r04.txt (r03_ab_studies.txt) r03a0*).
-  // G2 (5-ms accumulations, 1.2-ms level 0) never showed the slow mode and
-  // runs 1.5 % faster free-running (r03a0g2), so the wait is the G1 default;
-  // MSM_ACC_AFTER_L0=0 / =1 forces either schedule for both groups.
-  static const int l0_env = [] {
-    const char *e = getenv("MSM_ACC_AFTER_L0");
-    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-  }();
-  const bool l0_first = l0_env < 0 ? G == 1 : l0_env == 1;
-  // Fronts run up to nfr - 1 groups ahead on their own stream, but each is
-  // ENQUEUED after the accumulation before it: enqueuing the first nfr - 1
-  // fronts (7 launches each) before the first accumulation cost ~0.3 ms of host
-  // time at the start of a small-MSM batch (profiles/r05_small_trace.txt).
-  // Front g + 1 is always enqueued before accumulation g + 1 waits on it.
-  size_t fronts_issued = 0;
-  auto issue_fronts = [&](size_t upto) {  // every front group <= upto not yet enqueued
-    for (; fronts_issued <= upto && fronts_issued < nfg; ++fronts_issued) front_group(fronts_issued);
-  };
-  const size_t nphase = phase ? std::min(nfg, (size_t)nfr) : 1;  // fronts before the first accumulation
-  issue_fronts(nphase - 1);
-  // Two accumulation lanes (small MSMs, batch_lanes()): MSM k accumulates into
-  // bucket set k % 2 on lane stream k % 2 (the caller's s, tails_[0]) and its
-  // level 0 follows on the same stream, so accumulations k and k + 1 run side
-  // by side -- one small accumulation (a few hundred thousand buckets, one lane
-  // each) fills the chip's 3 x 1024 wave slots only ~1 round deep, and its last
-  // waves run alone -- while the group tails run on tails_[1].  Bucket set k % 2
-  // is reused by lane k % 2 only, in stream order; reducer set q % 2 is reused
-  // by group q + 2 after tail q (event evt[q]).
-  // Three lanes (MSM_BATCH_LANES=3) add tails_[1] as a lane and move the group
-  // tails to the front stream (the process has 4 hardware queues by default,
-  // GPU_MAX_HW_QUEUES: one stream per queue).
-  // Accumulation groups (small MSMs, one table for every job; MSM_ACC_GROUP=0
-  // selects the per-MSM lanes below): front group g's R_g sets accumulate in
-  // ONE launch (k_accumulate_sets, into bucket sets gbuckets_[g % 2]) on lane
-  // stream g % 2, then ONE level-0 launch per reduction group they touch; the
-  // reduction-group tails run on tails_[1].  A small MSM's own grid fills the
-  // chip's wave slots about one round deep and its last waves run with the chip
-  // half idle; side-by-side lanes left the accumulations at ~0.55 of the madd
-  // rate (2^17: 0.65 ms each, 1.5 running at a time; profiles/r05_small_trace.txt).
-  if (acc_groups) {
-    hipStream_t lane[2] = {s, tails_[0]}, ts = tails_[1];
-    for (size_t g = 0; g < nfg; ++g) {
-      copy_group(g + nsg);
-      const size_t k0 = fgb[g], k1 = fgb[g + 1];
-      const int gb = (int)(g & 1);
-      hipStream_t L = lane[gb];
-      MSM_HIP_CHECK(hipStreamWaitEvent(L, evf[g], 0));
-      if (g == 0 && nphase > 1) MSM_HIP_CHECK(hipStreamWaitEvent(L, evf[nphase - 1], 0));  // the front phase
-      if (prof) MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k0], L));
-      accumulate_sets(L, (int)(g % nfr), (int)(k1 - k0), gb, job_table(k0));
-      if (prof) {
-        MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k0 + 1], L));
-        prof_k.push_back(k0);
-      }
-      for (size_t k = k0; k < k1; ++k) MSM_HIP_CHECK(hipEventRecord(eva[k], L));
-      acc_enq = k1;
-      for (size_t a = k0; a < k1;) {  // level 0, one launch per reduction group touched
-        const size_t q = grp(a), b = std::min(k1, gfirst[q + 1]);
-        if (q >= (size_t)nred) MSM_HIP_CHECK(hipStreamWaitEvent(L, evt[q - nred], 0));  // reducer set free again
-        red.launch_head_slots(L, gbuckets_[gb].as<uint8_t>() + (a - k0) * NB * sizeof(Xyzz<typename FieldOf<G>::F>), NB,
-                              (int)(q % nred), (int)gslot(a), (int)(b - a));
-        a = b;
-      }
-      for (size_t k = k0; k < k1; ++k) MSM_HIP_CHECK(hipEventRecord(evh[k], L));
-      for (size_t k = k0; k < k1; ++k) {  // tails of the reduction groups ending in [k0, k1)
-        if (!gend(k)) continue;
-        const size_t q = grp(k), first = gfirst[q];
-        MSM_HIP_CHECK(hipStreamWaitEvent(ts, evh[k], 0));  // this lane's level 0s of group q
-        if (k0 >= 1 && k0 - 1 >= first) MSM_HIP_CHECK(hipStreamWaitEvent(ts, evh[k0 - 1], 0));  // the other lane's
-        group_tail(ts, (int)(q % nred), first, k - first + 1, k + 1 == count);
-        MSM_HIP_CHECK(hipEventRecord(evt[q], ts));
-      }
-      issue_fronts(g + nfr - 1);
-    }
-  }
-  if (nl >= 2 && !acc_groups) {
-    hipStream_t lane[3] = {s, tails_[0], tails_[1]}, ts = nl == 3 ? fstream_ : tails_[1];
-    for (size_t g = 0; g < nfg; ++g) {
-      copy_group(g + nsg);
-      for (size_t k = fgb[g]; k < fgb[g + 1]; ++k) {
-        hipStream_t L = lane[k % nl];
-        const size_t q = grp(k);
-        const int bset = (int)(k % nl), slot = (int)gslot(k), gset = (int)(q % nred);
-        MSM_HIP_CHECK(hipStreamWaitEvent(L, evf[g], 0));
-        if (q >= (size_t)nred && slot < nl)  // reducer set q % nred free again
-          MSM_HIP_CHECK(hipStreamWaitEvent(L, evt[q - nred], 0));
-        if (prof) MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k], L));
-        accumulate(L, (int)(g % nfr), (int)(k - fgb[g]), bset, job_table(k));
-        if (prof) {
-          MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k + 1], L));
-          prof_k.push_back(k);
-        }
-        MSM_HIP_CHECK(hipEventRecord(eva[k], L));
-        acc_enq = k + 1;
-        red.launch_head_slot(L, buckets_[bset].p, gset, slot);
-        MSM_HIP_CHECK(hipEventRecord(evh[k], L));
-        if (gend(k)) {  // the group's level 0s are done on both lanes
-          for (int d = 0; d < nl && d <= slot; ++d) MSM_HIP_CHECK(hipStreamWaitEvent(ts, evh[k - d], 0));
-          group_tail(ts, gset, k - slot, slot + 1, k + 1 == count);
-          MSM_HIP_CHECK(hipEventRecord(evt[q], ts));
-        }
-      }
-      issue_fronts(g + nfr - 1);
-    }
-  }
-  // Level 0 inside the next accumulation's grid (A/B knob, off by default:
-  // measured slower, resident 434-438 vs 446-450 M pairs/s, G2 164.4 vs 165.3 M,
-  // profiles/archive_r01_r04.txt (r04_l0_fuse_ab.txt); MSM_L0_FUSE=1: level-0 workgroups first, =2:
-  // last; k_accumulate_l0 / k_accumulate2p_l0): MSM k's launch also runs
-  // level 0 of MSM k - 1 on the caller's stream, the last MSM's level 0 runs
-  // alone after the loop, and reducer set q % 2 is reused by group q + 2 only
-  // after tail q (event evt[q]: level 0 no longer runs on the tail's stream).
-  static const int fuse_env = [] {
-    const char *e = getenv("MSM_L0_FUSE");
-    return e ? std::max(0, std::min(2, atoi(e))) : 0;
-  }();
-  const int fuse = nl < 2 ? fuse_env : 0;
-  auto l0_group_tail = [&](size_t p) {  // after level 0 of MSM p (recorded as evh[p] on s)
-    const size_t pq = grp(p), pslot = gslot(p);
-    if (!gend(p)) return;
-    hipStream_t ts = tails_[pq % 2];
-    MSM_HIP_CHECK(hipStreamWaitEvent(ts, evh[p], 0));
-    group_tail(ts, (int)(pq % 2), p - pslot, pslot + 1, p + 1 == count);
-    MSM_HIP_CHECK(hipEventRecord(evt[pq], ts));
-  };
-  auto l0_set_free = [&](size_t p) {  // level 0 of MSM p may write its reducer set
-    const size_t pq = grp(p);
-    if (gslot(p) == 0 && pq >= 2) MSM_HIP_CHECK(hipStreamWaitEvent(s, evt[pq - 2], 0));
-  };
-  for (size_t g = 0; g < (nl >= 2 || !fuse ? 0 : nfg); ++g) {
-    copy_group(g + nsg);
-    MSM_HIP_CHECK(hipStreamWaitEvent(s, evf[g], 0));
-    for (size_t k = fgb[g]; k < fgb[g + 1]; ++k) {
-      const int bset = (int)(k % kBSets);
-      if (k >= 1) l0_set_free(k - 1);
-      if (prof) MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k], s));
-      if (k >= 1)
-        accumulate_l0(s, (int)(g % nfr), (int)(k - fgb[g]), bset, job_table(k), (int)((k - 1) % kBSets),
-                      (int)(grp(k - 1) % 2), (int)gslot(k - 1), fuse == 2);
-      else
-        accumulate(s, (int)(g % nfr), (int)(k - fgb[g]), bset, job_table(k));
-      if (prof) {
-        MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k + 1], s));
-        prof_k.push_back(k);
-      }
-      MSM_HIP_CHECK(hipEventRecord(eva[k], s));
-      acc_enq = k + 1;
-      if (k >= 1) {
-        MSM_HIP_CHECK(hipEventRecord(evh[k - 1], s));
-        l0_group_tail(k - 1);
-      }
-    }
-    issue_fronts(g + nfr - 1);
-  }
-  if (fuse && nl < 2) {  // level 0 of the last MSM, alone
-    const size_t p = count - 1;
-    l0_set_free(p);
-    red.launch_head_slot(s, buckets_[p % kBSets].p, (int)(grp(p) % 2), (int)gslot(p));
-    MSM_HIP_CHECK(hipEventRecord(evh[p], s));
-    l0_group_tail(p);
-  }
-  for (size_t g = 0; g < (nl >= 2 || fuse ? 0 : nfg); ++g) {
-    copy_group(g + nsg);
-    MSM_HIP_CHECK(hipStreamWaitEvent(s, evf[g], 0));
-    for (size_t k = fgb[g]; k < fgb[g + 1]; ++k) {
-      const int bset = (int)(k % kBSets), slot = (int)gslot(k), gset = (int)(grp(k) % 2);
-      hipStream_t ts = tails_[gset];
-      if (k >= (size_t)kBSets) MSM_HIP_CHECK(hipStreamWaitEvent(s, evh[k - kBSets], 0));  // bucket set free again
-      if (l0_first && k >= 1) MSM_HIP_CHECK(hipStreamWaitEvent(s, evh[k - 1], 0));
-      if (prof) MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k], s));
-      accumulate(s, (int)(g % nfr), (int)(k - fgb[g]), bset, job_table(k));
-      if (prof) {
-        MSM_HIP_CHECK(hipEventRecord(acc_ev_[2 * k + 1], s));
-        prof_k.push_back(k);
-      }
-      MSM_HIP_CHECK(hipEventRecord(eva[k], s));
-      acc_enq = k + 1;
-      MSM_HIP_CHECK(hipStreamWaitEvent(ts, eva[k], 0));
-      red.launch_head_slot(ts, buckets_[bset].p, gset, slot);
-      MSM_HIP_CHECK(hipEventRecord(evh[k], ts));
-      if (gend(k)) {  // the reduction group's last MSM
-        group_tail(ts, gset, k - slot, slot + 1, k + 1 == count);
-      }
-    }
-    issue_fronts(g + nfr - 1);
-  }
-  // the caller's stream observes completion of every reduction (and front)
-  MSM_HIP_CHECK(hipEventRecord(ev_tail_[0], fstream_));
-  MSM_HIP_CHECK(hipStreamWaitEvent(s, ev_tail_[0], 0));
-  for (int t = 0; t < kBSets; ++t) {
-    MSM_HIP_CHECK(hipEventRecord(ev_tail_[t], tails_[t]));
-    MSM_HIP_CHECK(hipStreamWaitEvent(s, ev_tail_[t], 0));
-  }
-  for (int t = 0; t < kBSets; ++t) MSM_HIP_CHECK(hipStreamSynchronize(tails_[t]));
-  MSM_HIP_CHECK(hipStreamSynchronize(fstream_));  // three lanes: the group read-backs ran on the front stream
-  // the per-MSM host Horner (~20 us each) over the host worker threads: with
-  // one reduction group per batch every combine runs after the last tail
-  const size_t last_first = gfirst[ngroups - 1];  // the last group's MSMs: host_bits_ when bit_tail
-  auto combine_k = [&](size_t k) {
-    outs[k] = bit_tail && k >= last_first ? red.combine_bits((const uint8_t *)host_bits_ + (k - last_first) * bb)
-                                          : red.combine((const uint8_t *)host_out_ + k * ob)[0];
-  };
-  if (dev_out) {
-    // the window sums stay in dev_out for the caller's exchange
-  } else if (count >= 4) {
-    WorkerPool::get().parallel_for(count, combine_k);
-  } else {
-    for (size_t k = 0; k < count; ++k) combine_k(k);
-  }
+  BatchSink sink{*this,  p,          *batch_red_, {s, tails_[0], tails_[1], fstream_, cstream_},
+                 scalars, stride,    set_stride,  tables,
+                 static_cast<uint8_t *>(dev_out ? dev_out : host_out_), prof, {}};
+  BatchIssue<BatchSink>(p, sink).run();
   profile_ = prof;
-  if (prof) {  // accumulation time per MSM over the batch (HIP events on the accumulation streams)
-    float sum = 0;
-    for (size_t k : prof_k) {
-      float ms;
-      MSM_HIP_CHECK(hipEventSynchronize(acc_ev_[2 * k + 1]));
-      MSM_HIP_CHECK(hipEventElapsedTime(&ms, acc_ev_[2 * k], acc_ev_[2 * k + 1]));
-      sum += ms;
-    }
-    times_ = PhaseTimes();
-    times_.accumulate = sum / (float)count;
-    times_.accumulate_launches = (int)prof_k.size();
-  }
+  batch_finish(p, sink.prof_k, outs, dev_out != nullptr, prof);
 }
 
 template class Ches<MSM_GROUP>;

@@ -241,10 +241,7 @@ void Pippenger<G>::plan_reduction(int nbits) {
   // A/B knob: the batch reducer's level-0 chunk; 0 (default): red_'s own
   // (chunks of 2 at 2^16) -- with front groups of 4, 0.360 vs 0.385 ms per 2^16
   // MSM for chunks of 8 (profiles/r05_shard_pip_study.txt)
-  static const int bc_env = [] {
-    const char *e = getenv("MSM_PIP_L0_CHUNK");
-    return e ? std::max(0, std::min(64, atoi(e))) : 0;
-  }();
+  const int bc_env = BatchKnobs::env().pip_l0_chunk;
   if (bc_env && red_.level0_chunk() != bc_env) {
     bred_.plan(wt, win, W, bc_env);
     batch_red_ = &bred_;
@@ -297,21 +294,68 @@ void Pippenger<G>::run(hipStream_t s, const uint8_t *d_scalars, size_t stride, i
   back(s, nbits, out);
 }
 
+// The batch (run_batch) issues through the accumulation-group schedule of
+// batch_plan.hpp (BatchPlan::plain): front groups of up to fg_max
+// sets in ONE pass per stage (7 launches per group instead of per MSM), the
+// group's accumulations in ONE launch (k_accumulate_sets) and its level 0s in
+// one launch per reduction group.  A 2^16 MSM's front (digits + two-level sort
+// of 1.25 M entries) took as long as its accumulation beside the other lane's
+// work, so one front per MSM on the front stream set the period
+// (profiles/r05_small_trace.txt).
 template <int G>
-void Pippenger<G>::run_batch(hipStream_t s, const uint8_t *d_scalars, size_t stride, size_t set_stride, size_t count,
-                             int nbits, hfp::Jac<HF> *outs) {
+struct Pippenger<G>::BatchSink {
   typedef typename FieldOf<G>::F F;
-  DeviceGuard g(dev_);
-  if (nbits < 1 || nbits > 256) throw std::runtime_error("nbits must be in [1,256]");
-  if (count == 0) return;
-  if (n_ == 0) {
-    for (size_t k = 0; k < count; ++k) outs[k] = hfp::Jac<HF>{hfp::fzero(HF()), hfp::fzero(HF()), hfp::fzero(HF())};
-    return;
+  Pippenger &e;
+  const BatchPlan &p;
+  WeightedReducer<G> &red;
+  hipStream_t st[kBatchStreams];
+  const uint8_t *d_scalars;
+  size_t stride, set_stride;
+  int nbits;
+  size_t NT;
+  hfp::Jac<HF> *outs;
+
+  void wait(int s, size_t i) { MSM_HIP_CHECK(hipStreamWaitEvent(st[s], e.bev_[i], 0)); }
+  void record(size_t i, int s) { MSM_HIP_CHECK(hipEventRecord(e.bev_[i], st[s])); }
+  void host_wait(size_t i) { MSM_HIP_CHECK(hipEventSynchronize(e.bev_[i])); }
+  void sync(int) {}
+  void copy_set(size_t, size_t) {}
+  void front(size_t g) {
+    e.front(st[kFront], d_scalars + p.fgb[g] * set_stride, stride, nbits, nullptr, e.fs_[g % p.nfr],
+            (int)(p.fgb[g + 1] - p.fgb[g]), set_stride);
   }
+  void accumulate(int, size_t, size_t, int) {}
+  void accumulate_group(int s, size_t g, int gb) {  // bucket sets: lane gb only, in order
+    e.accumulate_sets(st[s], nbits, e.fs_[g % p.nfr], (int)(p.fgb[g + 1] - p.fgb[g]), e.gbuckets_[gb]);
+  }
+  void level0(int, int, int, int) {}
+  void level0_group(int s, int gb, size_t off, int rset, int slot0, int m) {
+    red.launch_head_slots(st[s], e.gbuckets_[gb].template as<uint8_t>() + off * NT * sizeof(Xyzz<F>), NT, rset, slot0, m);
+  }
+  void tail(int s, int rset, size_t first, size_t m, bool last) {
+    red.launch_tail_group(st[s], rset, (int)m, p.tail_coop && last);
+    red.copy_out_group(st[s], rset, (int)m, (uint8_t *)e.host_out_ + first * red.out_bytes());
+  }
+  void combine(size_t first, size_t m) {  // spread over the host worker threads
+    WorkerPool::get().parallel_for(m, [&](size_t i) {
+      outs[first + i] = red.combine_windows((const uint8_t *)e.host_out_ + (first + i) * red.out_bytes(), e.c_);
+    });
+  }
+  void prof_begin(int, size_t) {}
+  void prof_end(int, size_t) {}
+};
+
+// every buffer the pipeline touches exists before its first launch (an
+// allocation inside the issue loop would synchronise the device): read-back
+// slots, bucket sets for a whole front group on each lane, reducer sets, and
+// every front set sized for a whole group (sized by one untimed front of fg_max
+// copies of set 0, outside the pipeline)
+template <int G>
+void Pippenger<G>::batch_buffers(const BatchPlan &p, hipStream_t s, const uint8_t *d_scalars, size_t stride,
+                                 int nbits) {
+  typedef typename FieldOf<G>::F F;
   const int W = (nbits + 1 + c_ - 1) / c_;
-  const size_t NT = (size_t)W << (c_ - 1);
-  plan_reduction(nbits);
-  WeightedReducer<G> &red = *batch_red_;
+  const size_t NT = (size_t)W << (c_ - 1), ob = batch_red_->out_bytes();
   if (!fstream_) {
     int least = 0, greatest = 0;
     MSM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -319,141 +363,45 @@ void Pippenger<G>::run_batch(hipStream_t s, const uint8_t *d_scalars, size_t str
     MSM_HIP_CHECK(hipStreamCreateWithFlags(&lane1_, hipStreamNonBlocking));
     MSM_HIP_CHECK(hipStreamCreateWithFlags(&tstream_, hipStreamNonBlocking));
   }
-  // the dense stage of the batch's last group over 4 waves per add (nothing left
-  // to overlap it with; MSM_TAIL_COOP=0: one lane per add)
-  static const bool tail_coop = [] {
-    const char *e = getenv("MSM_TAIL_COOP");
-    return !e || atoi(e) != 0;
-  }();
-  // groups of R <= kGroup MSMs share one reduction tail (WeightedReducer batch groups)
-  static const size_t group_max = [] {  // A/B knob: MSMs per reduction group
-    const char *e = getenv("MSM_PIP_GROUP");
-    return (size_t)(e ? std::max(1, std::min(32, atoi(e))) : kGroup);
-  }();
-  // Front groups: the digits + sort of up to fg_max sets in ONE pass per stage
-  // (7 launches per group instead of per MSM), the group's accumulations in ONE
-  // launch (k_accumulate_sets) and its level 0s in one launch per reduction
-  // group.  A 2^16 MSM's front (digits + two-level sort of 1.25 M entries) took
-  // as long as its accumulation beside the other lane's work, so one front per
-  // MSM on the front stream set the period (profiles/r05_small_trace.txt).
-  // Groups ramp 1, 1, 2, 4, ... so the first accumulation starts after one
-  // front.  MSM_PIP_FRONT_GROUP=<1..8> (1: one MSM per launch, round 4's schedule).
-  static const size_t fg_env = [] {
-    const char *e = getenv("MSM_PIP_FRONT_GROUP");
-    return (size_t)(e ? std::max(1, std::min(8, atoi(e))) : 4);
-  }();
-  const size_t fg_max = fg_env;
-  const std::vector<size_t> fgb = front_groups(count, fg_max);
-  const size_t nfg = fgb.size() - 1;
-  const size_t ngroups = (count + group_max - 1) / group_max, R = (count + ngroups - 1) / ngroups;
-  const size_t ob = red.out_bytes();
-  if (host_out_bytes_ < count * ob) {
+  if (host_out_bytes_ < p.count * ob) {
     if (host_out_) (void)hipHostFree(host_out_);
     host_out_ = nullptr;
     host_out_bytes_ = 0;
-    const size_t bytes = std::max<size_t>(count, 64) * ob;
+    const size_t bytes = std::max<size_t>(p.count, 64) * ob;
     MSM_HIP_CHECK(hipHostMalloc(&host_out_, bytes, hipHostMallocDefault));
     host_out_bytes_ = bytes;
   }
-  // every buffer the pipeline touches exists before its first launch (an
-  // allocation inside the issue loop would synchronise the device): bucket
-  // sets for a whole front group on each lane, reducer sets, and every front
-  // set sized for a whole group (sized by one untimed front of fg_max copies of
-  // set 0, outside the pipeline)
-  // Front phase (MSM_FRONT_PHASE=1; off: measured slower, Ches::run_jobs): one
-  // front set per front group, up to kFrontPhase (~4 GiB of front sets at
-  // most), the first accumulation waiting for every front of the phase
-  static const bool phase_env = [] {
-    const char *e = getenv("MSM_FRONT_PHASE");
-    return e && atoi(e) != 0;
-  }();
-  const size_t fs_bytes = fg_max * (size_t)W * n_ * 24 + 1;  // ~ one front set (keys, vals, sorted, sort scratch)
-  const int nfr = phase_env ? (int)std::max<size_t>(kFronts, std::min<size_t>(kFrontPhase, ((size_t)4 << 30) / fs_bytes))
-                            : kFronts;
-  if ((int)fs_.size() < nfr) fs_.resize(nfr);
-  // the batch fronts' fine-pass workgroup (bucket_sort.hpp k_bs_fine): 1024
-  // threads, or MSM_PIP_FINE_BT=256 (fits beside the accumulation waves)
-  static const int fine_bt = [] {
-    const char *e = getenv("MSM_PIP_FINE_BT");
-    return e && atoi(e) == 256 ? 256 : 1024;
-  }();
-  for (ChesFrontSet &f : fs_) f.sort.fine_bt = fine_bt;
-  for (DevBuf &b : gbuckets_) b.ensure(fg_max * NT * sizeof(Xyzz<F>));
-  for (int t = 0; t < kRedSets; ++t) red.ensure_group(t, (int)group_max);
-  for (int f = 0; f < nfr; ++f)
-    if (fs_[f].sorted.bytes < (size_t)W * n_ * fg_max * 4 + 64)
-      front(s, d_scalars, stride, nbits, nullptr, fs_[f], (int)fg_max, 0);
+  for (ChesFrontSet &f : fs_) f.sort.fine_bt = p.fine_bt;
+  for (DevBuf &b : gbuckets_) b.ensure(p.fg_max * NT * sizeof(Xyzz<F>));
+  for (int t = 0; t < p.nred; ++t) batch_red_->ensure_group(t, (int)p.group_max);
+  for (int f = 0; f < p.nfr; ++f)
+    if (fs_[f].sorted.bytes < (size_t)W * n_ * p.fg_max * 4 + 64)
+      front(s, d_scalars, stride, nbits, nullptr, fs_[f], (int)p.fg_max, 0);
   MSM_HIP_CHECK(hipStreamSynchronize(s));
-  while (bev_.size() < 2 * count + nfg + ngroups + 1) {
+  while (bev_.size() < p.events) {
     hipEvent_t e;
     MSM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     bev_.push_back(e);
   }
-  hipEvent_t *eva = bev_.data() + 1, *evh = eva + count, *evf = evh + count, *evt = evf + nfg;
-  MSM_HIP_CHECK(hipEventRecord(bev_[0], s));
-  for (hipStream_t q : {fstream_, lane1_, tstream_}) MSM_HIP_CHECK(hipStreamWaitEvent(q, bev_[0], 0));
-  auto front_group = [&](size_t g) {
-    if (g >= nfg) return;
-    if (g >= (size_t)nfr)  // front set g % nfr: group g - nfr's accumulation has read it
-      MSM_HIP_CHECK(hipStreamWaitEvent(fstream_, eva[fgb[g - nfr + 1] - 1], 0));
-    front(fstream_, d_scalars + fgb[g] * set_stride, stride, nbits, nullptr, fs_[g % nfr],
-          (int)(fgb[g + 1] - fgb[g]), set_stride);
-    MSM_HIP_CHECK(hipEventRecord(evf[g], fstream_));
-  };
-  // accumulation groups alternate between two lane streams (the caller's and
-  // lane1_); group tails on tstream_
-  hipStream_t lane[2] = {s, lane1_};
-  // fronts run up to kFronts - 1 groups ahead, each ENQUEUED after the
-  // accumulation before it (enqueuing four fronts before the first accumulation
-  // cost ~0.3 ms of host time per batch); front g + 1 is always enqueued before
-  // accumulation g + 1 waits on it
-  size_t fronts_issued = 0;
-  auto issue_fronts = [&](size_t upto) {
-    for (; fronts_issued <= upto && fronts_issued < nfg; ++fronts_issued) front_group(fronts_issued);
-  };
-  const size_t nphase = phase_env ? std::min(nfg, (size_t)nfr) : 1;  // fronts before the first accumulation
-  issue_fronts(nphase - 1);
-  for (size_t g = 0; g < nfg; ++g) {
-    const size_t k0 = fgb[g], k1 = fgb[g + 1];
-    const int gb = (int)(g & 1);
-    hipStream_t L = lane[gb];
-    MSM_HIP_CHECK(hipStreamWaitEvent(L, evf[g], 0));
-    if (g == 0 && nphase > 1) MSM_HIP_CHECK(hipStreamWaitEvent(L, evf[nphase - 1], 0));  // the front phase
-    accumulate_sets(L, nbits, fs_[g % nfr], (int)(k1 - k0), gbuckets_[gb]);  // bucket sets: lane gb only, in order
-    for (size_t k = k0; k < k1; ++k) MSM_HIP_CHECK(hipEventRecord(eva[k], L));
-    for (size_t a = k0; a < k1;) {  // level 0, one launch per reduction group touched
-      const size_t q = a / R, b = std::min(k1, (q + 1) * R);
-      if (q >= (size_t)kRedSets) MSM_HIP_CHECK(hipStreamWaitEvent(L, evt[q - kRedSets], 0));  // reducer set free again
-      red.launch_head_slots(L, gbuckets_[gb].as<uint8_t>() + (a - k0) * NT * sizeof(Xyzz<F>), NT,
-                            (int)(q % kRedSets), (int)(a % R), (int)(b - a));
-      a = b;
-    }
-    for (size_t k = k0; k < k1; ++k) MSM_HIP_CHECK(hipEventRecord(evh[k], L));
-    for (size_t k = k0; k < k1; ++k) {  // tails of the reduction groups ending in [k0, k1)
-      if ((k + 1) % R != 0 && k + 1 != count) continue;
-      const size_t q = k / R, first = q * R;
-      MSM_HIP_CHECK(hipStreamWaitEvent(tstream_, evh[k], 0));                                     // this lane's level 0s
-      if (k0 >= 1 && k0 - 1 >= first) MSM_HIP_CHECK(hipStreamWaitEvent(tstream_, evh[k0 - 1], 0));  // the other lane's
-      red.launch_tail_group(tstream_, (int)(q % kRedSets), (int)(k - first + 1), tail_coop && k + 1 == count);
-      red.copy_out_group(tstream_, (int)(q % kRedSets), (int)(k - first + 1), (uint8_t *)host_out_ + first * ob);
-      MSM_HIP_CHECK(hipEventRecord(evt[q], tstream_));
-    }
-    issue_fronts(g + nfr - 1);
+}
+
+template <int G>
+void Pippenger<G>::run_batch(hipStream_t s, const uint8_t *d_scalars, size_t stride, size_t set_stride, size_t count,
+                             int nbits, hfp::Jac<HF> *outs) {
+  DeviceGuard g(dev_);
+  if (nbits < 1 || nbits > 256) throw std::runtime_error("nbits must be in [1,256]");
+  if (count == 0) return;
+  if (n_ == 0) {
+    for (size_t k = 0; k < count; ++k) outs[k] = hfp::Jac<HF>{hfp::fzero(HF()), hfp::fzero(HF()), hfp::fzero(HF())};
+    return;
   }
-  // the host Horner of group q (one per MSM, ~W c doublings each) overlaps the
-  // GPU work of later groups, spread over the host worker threads
-  for (size_t q = 0; q * R < count; ++q) {
-    MSM_HIP_CHECK(hipEventSynchronize(evt[q]));
-    const size_t k0 = q * R, k1 = std::min(count, (q + 1) * R);
-    WorkerPool::get().parallel_for(k1 - k0, [&](size_t i) {
-      outs[k0 + i] = red.combine_windows((const uint8_t *)host_out_ + (k0 + i) * ob, c_);
-    });
-  }
-  // the caller's stream observes completion of every stream of the batch
-  for (hipStream_t q : {fstream_, lane1_, tstream_}) {
-    MSM_HIP_CHECK(hipEventRecord(bev_[0], q));
-    MSM_HIP_CHECK(hipStreamWaitEvent(s, bev_[0], 0));
-  }
+  plan_reduction(nbits);
+  const BatchPlan p = BatchPlan::plain(count, BatchKnobs::env());
+  batch_buffers(p, s, d_scalars, stride, nbits);
+  const size_t NT = (size_t)((nbits + 1 + c_ - 1) / c_) << (c_ - 1);
+  BatchSink sink{*this, p, *batch_red_, {s, lane1_, tstream_, fstream_, nullptr}, d_scalars, stride, set_stride, nbits,
+                 NT,    outs};
+  BatchIssue<BatchSink>(p, sink).run();
 }
 
 // The blst drop-in (abi.cpp blst_p{1,2}s_mult_pippenger / _tile_pippenger):

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "acc_sched.hpp"
+#include "batch_plan.hpp"
 #include "host_fp.hpp"
 
 #define MSM_HIP_CHECK(x)                                                                           \
@@ -25,35 +26,6 @@ namespace msm {
 class HostStager;  // hoststage.hpp: pinned-ring uploads from pageable caller memory
 
 inline unsigned nblk(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
-// Front groups of a batch (MSMs [fgb[g], fgb[g + 1]) share one digits + sort
-// pass and, for small MSMs, one accumulation launch): 1, 1, 2, 4, then fg_max
-// each.  taper (MSM_FRONT_TAPER=1, A/B knob): the last group split in halves
-// down to one MSM (4 -> 2, 1, 1), so the level 0 that follows the batch's last
-// accumulation covers one MSM and the earlier level 0s run beside the last
-// accumulations.  Measured no better (2^17 shard 0.429 / 0.411 vs 0.414 / 0.436
-// ms, configs[1] 0.340 / 0.341 vs 0.334 / 0.339; profiles/r06_taper_prefetch_ab.txt).
-inline std::vector<size_t> front_groups(size_t count, size_t fg_max) {
-  static const bool taper = [] {
-    const char *e = getenv("MSM_FRONT_TAPER");
-    return e && atoi(e) != 0;
-  }();
-  std::vector<size_t> fgb{0};
-  while (fgb.back() < count)
-    fgb.push_back(std::min(count, fgb.back() + std::min<size_t>(fg_max, std::max<size_t>(1, fgb.back()))));
-  if (taper && fgb.size() >= 2) {
-    size_t first = fgb[fgb.size() - 2], len = count - first;
-    fgb.pop_back();
-    while (len > 1) {
-      const size_t half = (len + 1) / 2;
-      fgb.push_back(first + half);
-      first += half;
-      len -= half;
-    }
-    fgb.push_back(count);
-  }
-  return fgb;
-}
 
 struct DevBuf {
   void *p = nullptr;
@@ -254,8 +226,7 @@ class WeightedReducer {
   // level 0 of nmsm consecutive MSMs (slots slot0 .. slot0 + nmsm - 1 of set
   // `set`) in one launch; MSM j's buckets at S + j sstride points
   void launch_head_slots(hipStream_t s, const void *S, size_t sstride, int set, int slot0, int nmsm);
-  // the operands launch_head_slot would pass to its k_segsum (level 0 into slot
-  // `slot` of set `set`), for a caller that runs level 0 inside another grid
+  // the operands of level 0 into slot `slot` of set `set` (k_segsum)
   struct HeadArgs {
     const uint32_t *idx, *starts;
     void *dst;
@@ -356,14 +327,9 @@ class Pippenger {
   size_t n_ = 0;
   bool profile_ = false;
   PhaseTimes times_;
-  // kGroup: MSMs per reduction group; 10 (two tails for the 20-MSM configs[1]
-  // batch) since the host Horner of a group runs on the worker threads: 0.327-
-  // 0.339 vs 0.341-0.353 ms per 2^16 MSM with 8 (profiles/r05_pip_group_ab.txt)
-  static constexpr int kFronts = 5, kGroup = 10, kRedSets = 4;
-  // digit/sort outputs: fs_[0] for run(); run_batch rotates kFronts of them, or
-  // with the front phase one per front group (up to kFrontPhase)
+  static constexpr int kFronts = PlainBatch::kFronts;
+  // digit/sort outputs: fs_[0] for run(); run_batch rotates kFronts of them
   std::vector<ChesFrontSet> fs_ = std::vector<ChesFrontSet>(kFronts);
-  static constexpr int kFrontPhase = 16;
   DevBuf pts_, buckets_[2], tmp_, scal_;
   std::unique_ptr<HostStager> stage_;  // run_host: uploads from the caller's pageable memory
   hipStream_t up_ = nullptr;  // run_host: point upload stream
@@ -383,6 +349,8 @@ class Pippenger {
   // the R sets of a front group in one launch, set r's buckets at r NT in bk
   void accumulate_sets(hipStream_t s, int nbits, ChesFrontSet &f, int R, DevBuf &bk);
   DevBuf gbuckets_[2];  // run_batch accumulation groups: two lanes x front-group bucket sets
+  struct BatchSink;  // run_batch: the issue loop's operations (batch_plan.hpp) as HIP calls
+  void batch_buffers(const BatchPlan &p, hipStream_t s, const uint8_t *d_scalars, size_t stride, int nbits);
   void plan_reduction(int nbits);  // reducer plan for this window layout (built once)
   void back(hipStream_t s, int nbits, hfp::Jac<HF> *out);  // accumulate + reduce + read-back (fs_[0])
   WeightedReducer<G> red_;
@@ -427,7 +395,7 @@ class Ches {
   // sets are copied into device slots on their own copy stream (cstream_), ahead
   // of the group's front and overlapping earlier accumulations (pinned host
   // memory for a truly asynchronous copy).  Pipelined: front group g + 1 (digits
-  // + sort of up to kFrontGroup sets in one pass) beside group g's
+  // + sort of up to ChesBatch::kFrontGroup sets in one pass) beside group g's
   // accumulations, MSM k's reduction on a second stream beside MSM k+1's
   // accumulation.
   // dev_out (device memory of this engine's device, count * exchange_bytes()):
@@ -473,35 +441,13 @@ class Ches {
   void plan_buckets(size_t n);
   bool profile_ = false;
   PhaseTimes times_;
-  // bucket sets: MSM k accumulates into set k % kBSets while the reduction of
-  // MSM k-1 still reads the other one
-  static constexpr int kBSets = 2;
+  static constexpr int kBSets = ChesBatch::kBSets, kFrontsMax = ChesBatch::kFrontsMax;  // batch_plan.hpp
   static constexpr int kLanesMax = 3;  // batch accumulation lanes (batch_lanes), one bucket set each
   DevBuf code_, rank_, table_, buckets_[kLanesMax];
-  // digit/sort outputs.  A batch can run the fronts (digits + sort) of up to
-  // kFrontGroup MSMs in ONE pass per stage (seven launches for the group instead
-  // of seven per MSM), front group g+2 beside group g's accumulations, three
-  // front sets in rotation.  Measured on MI355X (tools/ab_env.sh, profiles/
-  // r03_front_group_ab.txt) the grouped fronts slow the accumulations they run
-  // beside more than the launches they save (resident 2.33-2.38 ms per MSM with
-  // groups of 8 vs 2.26-2.27 with groups of 1), so the default group is one
-  // MSM; MSM_FRONT_GROUP=<2..8> selects larger groups.  The synchronous MSM uses
-  // set 0 with one scalar set.
-  // batch: MSMs per reduction group (WeightedReducer::launch_tail_group).  20:
-  // a batch of up to 20 runs one tail, after its last accumulation, instead of
-  // tails beside accumulations (each costs the one beside it ~0.3 ms); 20 vs
-  // 8 measured +1.2 % (profiles/archive_r01_r04.txt (r04_red_group_ab.txt)).  MSM_RED_GROUP overrides.
-  static constexpr int kGroup = 20;
-  static constexpr int kFrontGroup = 8;  // batch: largest front group (ramping up 1, 1, 2, 4, 8)
-  static constexpr int kFrontGroupDefault = 1;
-  // front k+1 may start when accumulation k-2 ends (slack for the copies); the
-  // lane schedule of small MSMs rotates kFrontsMax sets (fronts further ahead)
-  static constexpr int kFronts = 3, kFrontsMax = 5;
-  // front sets: kFronts / kFrontsMax in rotation, or with the front phase of
-  // the small-MSM batch one per front group (up to kFrontPhase)
+  // digit/sort outputs: the synchronous MSM uses set 0 with one scalar set, a
+  // batch rotates BatchPlan::nfr of them, each sized for a whole front group
   std::vector<ChesFrontSet> fs_ = std::vector<ChesFrontSet>(kFrontsMax);
-  static constexpr int kFrontPhase = 16;
-  // host scalar sets of a batch: two groups of kFrontGroup device slots, copied on
+  // host scalar sets of a batch: BatchPlan::slot_groups groups of device slots, copied on
   // their own stream (cstream_) ahead of the group's front
   DevBuf scal_;
   DevBuf prime_;  // target of the one-time stream priming launches (run_batch)
@@ -535,11 +481,16 @@ class Ches {
   // accumulation group: sets 0 .. R-1 of front set `set` in one launch into
   // the R consecutive bucket sets of gbuckets_[gb]
   void accumulate_sets(hipStream_t s, int set, int R, int gb, const void *table);
-  DevBuf gbuckets_[2];  // accumulation groups: two lanes x kFrontGroup bucket sets
-  // batch: accumulation as above in the same grid as level 0 of the MSM whose
-  // buckets are in l0_bset, into reducer set gset / slot (k_accumulate_l0)
-  void accumulate_l0(hipStream_t s, int set, int r, int bset, const void *table, int l0_bset, int gset, int slot,
-                     int l0_last);
+  DevBuf gbuckets_[2];  // accumulation groups: two lanes x BatchPlan::fg_max bucket sets
+  // run_jobs in steps: the batch's streams (first call), its plan
+  // (batch_plan.hpp), buffers and events, the issue loops through BatchSink
+  // (each operation as its HIP call), then the host combine and profiling read-out
+  struct BatchSink;
+  void batch_streams();
+  BatchPlan batch_plan(size_t nsets, size_t nseg, size_t stride, size_t set_stride, bool scalars_on_host,
+                       bool dev_out) const;
+  void batch_buffers(const BatchPlan &p, hipStream_t s, size_t stride);
+  void batch_finish(const BatchPlan &p, const std::vector<size_t> &prof_k, hfp::Jac<HF> *outs, bool dev_out, bool prof);
 };
 
 // BGMW95 fixed-base variant (ref main_p1.cpp:94-122, 294-398;

@@ -235,24 +235,6 @@ static __global__ void __launch_bounds__(256, MSM_SEGSUM2P_WAVES)
   // MSM blockIdx.y of a batch group (k_segsum)
   segsum_pair(src + blockIdx.y * src_stride, idx, starts, dst + blockIdx.y * dst_stride, t);
 }
-// k_accumulate_l0 (ches_kernels.hpp) for G2: level 0 of the previous MSM and
-// this MSM's accumulation in one grid, both on lane pairs
-template <class PT>
-__global__ void __launch_bounds__(256)
-    k_accumulate2p_l0(const AccSched S, const PT *__restrict__ pts, Xyzz<Fp2> *__restrict__ buckets, size_t nbuckets,
-                      const Xyzz<Fp2> *__restrict__ l0src, const uint32_t *__restrict__ l0idx,
-                      const uint32_t *__restrict__ l0starts, Xyzz<Fp2> *__restrict__ l0dst, size_t l0out,
-                      uint32_t l0blocks, int l0_last) {
-  const uint32_t nacc = gridDim.x - l0blocks;
-  const bool l0 = l0_last ? blockIdx.x >= nacc : blockIdx.x < l0blocks;
-  const uint32_t b = l0 ? (l0_last ? blockIdx.x - nacc : blockIdx.x) : (l0_last ? blockIdx.x : blockIdx.x - l0blocks);
-  const size_t t = (size_t)b * blockDim.x + threadIdx.x;
-  if (l0) {
-    if (t < 2 * l0out) segsum_pair(l0src, l0idx, l0starts, l0dst, t);
-  } else if (t < 2 * nbuckets) {
-    accumulate_pair(S, pts, buckets, t);
-  }
-}
 
 // k_suffix_step / k_pair_step (ches_kernels.hpp) for G2 with two lanes per output
 static __global__ void __launch_bounds__(64)

@@ -16,13 +16,11 @@ for k in _Z11k_op_fp_mulP k_op_fp_sqr k_op_fp_mul2 k_op_g2l_mul_bs k_op_g2l_sqr 
 echo "# accumulation kernels as built (ches.hip, MSM_GROUP=1 / 2)"
 python3 $R/tools/isa_count.py $T/ches1.s k_accumulate
 python3 $R/tools/isa_count.py $T/ches2.s k_accumulate2p
-echo "# segment sums of the reduction as built (level 0: k_segsum / k_accumulate_l0; G2: k_segsum2p)"
+echo "# segment sums of the reduction as built (level 0: k_segsum; G2: k_segsum2p)"
 python3 $R/tools/isa_count.py $T/ches1.s 8k_segsumI
-python3 $R/tools/isa_count.py $T/ches1.s k_accumulate_l0
 python3 $R/tools/isa_count.py $T/ches2.s 10k_segsum2p
 echo "# registers and occupancy (waves per SIMD) of the same kernels"
 python3 $R/tools/kernel_resources.py $T/ches1.s 8k_segsumI
-python3 $R/tools/kernel_resources.py $T/ches1.s k_accumulate_l0
 python3 $R/tools/kernel_resources.py $T/ches2.s 10k_segsum2p
 python3 $R/tools/kernel_resources.py $T/ches1.s 12k_accumulateILi1
 # the G1 kernels under the column-form knobs (MSM_ACC_CHAIN, MSM_SEGSUM_CHAIN; fp.hpp MulChain)
@@ -31,7 +29,7 @@ for cfg in "-DMSM_ACC_CHAIN=0 -DMSM_SEGSUM_CHAIN=0" "-DMSM_ACC_CHAIN=1 -DMSM_SEG
            "-DMSM_ACC_CHAIN=0 -DMSM_SEGSUM_CHAIN=1" "-DMSM_ACC_CHAIN=1 -DMSM_SEGSUM_CHAIN=0 -DMSM_ACC_WAVES=4"; do
   $HIPCC -DMSM_GROUP=1 $cfg -o $T/ches1v.s $R/msm_blst_amd/csrc/ches.hip
   echo "# column forms: $cfg"
-  for k in 12k_accumulateILi1 8k_segsumI k_accumulate_l0; do
+  for k in 12k_accumulateILi1 8k_segsumI; do
     python3 $R/tools/isa_count.py $T/ches1v.s $k
     python3 $R/tools/kernel_resources.py $T/ches1v.s $k
   done

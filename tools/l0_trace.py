@@ -20,7 +20,7 @@ def grid(r):
 def main(path, K=20):
     rows = list(csv.DictReader(open(path)))
     ev = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], grid(r)) for r in rows)
-    # (demangled or mangled names; k_accumulate_l0, k_segsum2p and the _c forms do not match)
+    # (demangled or mangled names; k_segsum2p and the _c forms do not match)
     acc = [e for e in ev if "k_accumulate<" in e[2] or "k_accumulateILi" in e[2]][-K:]
     seg = [e for e in ev if "k_segsum<" in e[2] or "k_segsumILi" in e[2]]
     t0 = acc[0][0]
