@@ -54,7 +54,7 @@ struct BatchKnobs {
   // MSMs per reduction group, MSM_RED_GROUP (CHES) and MSM_PIP_GROUP (plain),
   // 1..32; default ChesBatch::kGroup and PlainBatch::kGroup
   int red_group = 0, pip_group = 0;
-  // The batch's LAST reduction group ends in bit sums (launch_tail_group_bits):
+  // The batch's LAST reduction group ends in bit sums (WeightedReducer::tail, kEndBits):
   // its tail runs after the last accumulation with the chip otherwise idle, and
   // the bit phase is ~10 latency-bound levels instead of the dense stage's 2 s
   // (profiles/r06_small_trace.txt).  Earlier groups keep the dense stage: their

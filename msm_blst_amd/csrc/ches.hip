@@ -3,7 +3,8 @@
 // ref main_p1.cpp:192-246) on one MI355X.
 //
 // Setup (once per context): parameters of ref ches_config_files, bucket set B
-// (ref auxiliaryfunc.h:257-288), digit hash (ref main_p1.cpp:140-152) and the
+// (ref auxiliaryfunc.h:257-288), digit hash (ref main_p1.cpp:140-152), all three
+// group-independent host code in ches_setup.hpp, and the
 // precomputed table T[3(i h + j) + m - 1] = m q^j P_i (ref main_p1.cpp:155-172),
 // the latter built on the GPU and kept resident in HBM in the engine's
 // internal limb layout.
@@ -32,103 +33,7 @@
 
 namespace msm {
 
-#if MSM_GROUP == 1  // group-independent host setup: compiled once
-// ------------------------------------------------------------- parameters --
-// values of ref ches_config_files/config_file_n_exp_{8..21}.h and the _beta
-// variants (n_exp, beta, q exponent, h, a_h, d_max, |B|, BGMW95 q exponent, h)
-static const ChesParams kChesTable[] = {
-    {8, 0, 12, 22, 7, 6, 857, 10, 26},         {9, 0, 13, 20, 231, 6, 1725, 11, 24},
-    {10, 0, 13, 20, 231, 6, 1725, 12, 22},     {11, 0, 14, 19, 7, 6, 3417, 13, 20},
-    {12, 0, 14, 19, 7, 6, 3417, 13, 20},       {13, 0, 16, 16, 29677, 6, 18343, 15, 17},
-    {14, 0, 16, 16, 29677, 6, 18343, 15, 17},  {15, 0, 16, 16, 29677, 6, 18343, 16, 16},
-    {16, 0, 19, 14, 231, 6, 109244, 17, 15},   {16, 1, 18, 15, 7, 6, 54618, 17, 15},
-    {17, 0, 20, 13, 29677, 6, 220931, 17, 15}, {17, 1, 19, 14, 231, 6, 109244, 17, 15},
-    {18, 0, 20, 13, 29677, 6, 220931, 19, 14}, {19, 0, 20, 13, 29677, 6, 220931, 20, 13},
-    {20, 0, 22, 12, 7419, 6, 874437, 20, 13},  {20, 1, 20, 13, 29677, 6, 220931, 20, 13},
-    {21, 0, 22, 12, 7419, 6, 874437, 22, 12},
-};
-
-bool ches_params_for(int n_exp, int beta, ChesParams *out) {
-  for (const ChesParams &p : kChesTable)
-    if (p.n_exp == n_exp && p.beta == beta) {
-      *out = p;
-      return true;
-    }
-  return false;
-}
-
-// omega2(v) + omega3(v) even  (ref auxiliaryfunc.h:217-255)
-static bool even23(int v) {
-  int e = 0;
-  while (v % 2 == 0) v /= 2, ++e;
-  while (v % 3 == 0) v /= 3, ++e;
-  return (e & 1) == 0;
-}
-
-// ref auxiliaryfunc.h:257-288: {0,1} u {i <= q/2 : even23(i)}, then the two
-// pruning passes (membership tested as the passes run, as std::set::erase
-// does there), then every even23 value <= a_h + 1 re-inserted.
-std::vector<int> ches_bucket_set(int q, int a_h) {
-  size_t lim = std::max<size_t>((size_t)q / 2 + 1, (size_t)a_h + 2);
-  std::vector<uint8_t> in(lim, 0);
-  in[0] = in[1] = 1;
-  for (int i = 2; i <= q / 2; ++i) in[i] = even23(i);
-  for (int i = q / 4; i < q / 2; ++i) {
-    int t = q - 2 * i;
-    if (in[i] && t >= 0 && (size_t)t < lim && in[t]) in[t] = 0;
-  }
-  for (int i = q / 6; i < q / 4; ++i) {
-    int t = q - 3 * i;
-    if (in[i] && t >= 0 && (size_t)t < lim && in[t]) in[t] = 0;
-  }
-  for (int i = 1; i <= a_h + 1; ++i)
-    if (even23(i)) in[i] = 1;
-  std::vector<int> B;
-  for (size_t v = 0; v < lim; ++v)
-    if (in[v]) B.push_back((int)v);
-  return B;
-}
-
-// ref main_p1.cpp:140-152: every (m, b) writes H[q - m b] = (m, b, alpha=1),
-// then H[m b] = (m, b, 0); later writes win.  Packed per ches_kernels.hpp.
-std::vector<uint32_t> ches_digit_hash(const std::vector<int> &B, int q) {
-  std::vector<uint32_t> H((size_t)q + 1, 0);
-  for (int alpha = 1; alpha >= 0; --alpha)
-    for (int m = 1; m <= 3; ++m)
-      for (size_t i = 0; i < B.size(); ++i) {
-        long mb = (long)m * B[i];
-        if (mb > q) continue;
-        size_t d = alpha ? (size_t)(q - mb) : (size_t)mb;
-        H[d] = (uint32_t)i | ((uint32_t)(m - 1) << 24) | ((uint32_t)alpha << 31);
-      }
-  return H;
-}
-
-void ches_digit_code(const std::vector<int> &B, int q, std::vector<uint32_t> &code, std::vector<uint32_t> &rank) {
-  const std::vector<uint32_t> H = ches_digit_hash(B, q);
-  code.assign(((size_t)q >> 3) + 2, 0);
-  for (size_t d = 0; d <= (size_t)q; ++d) {
-    const uint32_t m = ((H[d] >> 24) & 3u) + 1, alpha = H[d] >> 31;
-    const int b = B[H[d] & CH_IDX_MASK];
-    uint32_t c = (m - 1) | (alpha << 2);
-    if (b == 0) {
-      c |= 8u;  // bucket value 0: entry skipped
-    } else {
-      const long v = alpha ? (long)q - (long)d : (long)d;
-      if (v % m != 0 || v / m != b) throw std::runtime_error("CHES digit map is not arithmetic at d=" + std::to_string(d));
-    }
-    code[d >> 3] |= c << (4 * (d & 7));
-  }
-  const size_t words = ((size_t)B.back() >> 5) + 1;
-  rank.assign(2 * words, 0);
-  for (int v : B) rank[2 * ((size_t)v >> 5)] |= 1u << (v & 31);
-  uint32_t run = 0;
-  for (size_t w = 0; w < words; ++w) {
-    rank[2 * w + 1] = run;
-    run += (uint32_t)__builtin_popcount(rank[2 * w]);
-  }
-}
-#endif  // MSM_GROUP == 1
+static_assert(kChesHashIdxMask == CH_IDX_MASK, "ches_setup.hpp and ches_kernels.hpp disagree on the digit hash layout");
 
 // a tail level of segment sums: few outputs are latency-bound, so one add
 // spreads over 4 waves (coop.hpp: G1 one lane per wave, G2 a lane pair per wave);
@@ -164,456 +69,170 @@ static size_t dense_coop_max() {
   return v;
 }
 
+// One step of the dense stage.  coop: one add over 4 waves (coop.hpp), for
+// steps of at most dense_coop_max() adds; else one add per lane (G2: per lane
+// pair, fp2l.hpp).  A suffix step is W S adds, a pair step `half`.
 template <int G>
-void ScanReducer<G>::launch(hipStream_t s, const void *Abuf, int W, int S, bool coop_req) {
+static void launch_suffix_step(hipStream_t s, const Xyzz<typename FieldOf<G>::F> *src,
+                               Xyzz<typename FieldOf<G>::F> *dst, int S, int d, int W, bool coop) {
+  const size_t NT = (size_t)W * S;
+  coop = coop && NT <= dense_coop_max();
+  if constexpr (G == 2) {
+    if (coop) hipLaunchKernelGGL(k_suffix_step_c2p, dim3(nblk(NT, 32)), dim3(256), 0, s, src, dst, S, d, W);
+    else hipLaunchKernelGGL(k_suffix_step2p, dim3(nblk(2 * NT, 64)), dim3(64), 0, s, src, dst, S, d, W);
+  } else {
+    if (coop) hipLaunchKernelGGL(k_suffix_step_c<G>, dim3(nblk(NT, 64)), dim3(256), 0, s, src, dst, S, d, W);
+    else hipLaunchKernelGGL(k_suffix_step<G>, dim3(nblk(NT, 64)), dim3(64), 0, s, src, dst, S, d, W);
+  }
+}
+template <int G>
+static void launch_pair_step(hipStream_t s, const Xyzz<typename FieldOf<G>::F> *src, Xyzz<typename FieldOf<G>::F> *dst,
+                             size_t half, bool coop) {
+  coop = coop && half <= dense_coop_max();
+  if constexpr (G == 2) {
+    if (coop) hipLaunchKernelGGL(k_pair_step_c2p, dim3(nblk(half, 32)), dim3(256), 0, s, src, dst, half);
+    else hipLaunchKernelGGL(k_pair_step2p, dim3(nblk(2 * half, 64)), dim3(64), 0, s, src, dst, half);
+  } else {
+    if (coop) hipLaunchKernelGGL(k_pair_step_c<G>, dim3(nblk(half, 64)), dim3(256), 0, s, src, dst, half);
+    else hipLaunchKernelGGL(k_pair_step<G>, dim3(nblk(half, 64)), dim3(64), 0, s, src, dst, half);
+  }
+}
+
+template <int G>
+void ScanReducer<G>::launch(hipStream_t s, const void *Abuf, int W, int S, bool coop) {
   typedef typename FieldOf<G>::F F;
   if (S < 1 || (S & (S - 1))) throw std::runtime_error("ScanReducer: S must be a power of two");
   const size_t NT = (size_t)W * S;
-  bool coop = coop_req && NT <= dense_coop_max();  // the suffix steps: NT adds each
   buf[0].ensure(NT * sizeof(Xyzz<F>));
   buf[1].ensure(NT * sizeof(Xyzz<F>));
   fin.ensure((size_t)W * 144 * G);
   const Xyzz<F> *src = reinterpret_cast<const Xyzz<F> *>(Abuf);
   int cur = 0;
-  for (int d = 1; d < S; d <<= 1) {  // suffix sums T_k = sum_{b >= k} A_b
+  auto step = [&](auto &&launch_step) {
     Xyzz<F> *dst = buf[cur].as<Xyzz<F>>();
-    if constexpr (G == 2) {  // lane pairs (fp2l.hpp); coop: one add over 4 waves (coop.hpp)
-      if (coop)
-        hipLaunchKernelGGL(k_suffix_step_c2p, dim3(nblk(NT, 32)), dim3(256), 0, s, src, dst, S, d, W);
-      else
-        hipLaunchKernelGGL(k_suffix_step2p, dim3(nblk(2 * NT, 64)), dim3(64), 0, s, src, dst, S, d, W);
-    } else {
-      if (coop) hipLaunchKernelGGL(k_suffix_step_c<G>, dim3(nblk(NT, 64)), dim3(256), 0, s, src, dst, S, d, W);
-      else hipLaunchKernelGGL(k_suffix_step<G>, dim3(nblk(NT, 64)), dim3(64), 0, s, src, dst, S, d, W);
-    }
+    launch_step(dst);
     MSM_HIP_CHECK(hipGetLastError());
     src = dst;
     cur ^= 1;
-  }
-  for (size_t len = NT; len > (size_t)W; len >>= 1) {  // sum_k T_k = sum_b b A_b
-    Xyzz<F> *dst = buf[cur].as<Xyzz<F>>();
-    coop = coop_req && len / 2 <= dense_coop_max();  // this pair step: len / 2 adds
-    if constexpr (G == 2) {
-      if (coop)
-        hipLaunchKernelGGL(k_pair_step_c2p, dim3(nblk(len / 2, 32)), dim3(256), 0, s, src, dst, len / 2);
-      else
-        hipLaunchKernelGGL(k_pair_step2p, dim3(nblk(len, 64)), dim3(64), 0, s, src, dst, len / 2);
-    } else {
-      if (coop) hipLaunchKernelGGL(k_pair_step_c<G>, dim3(nblk(len / 2, 64)), dim3(256), 0, s, src, dst, len / 2);
-      else hipLaunchKernelGGL(k_pair_step<G>, dim3(nblk(len / 2, 64)), dim3(64), 0, s, src, dst, len / 2);
-    }
-    MSM_HIP_CHECK(hipGetLastError());
-    src = dst;
-    cur ^= 1;
-  }
+  };
+  for (int d = 1; d < S; d <<= 1)  // suffix sums T_k = sum_{b >= k} A_b
+    step([&](Xyzz<F> *dst) { launch_suffix_step<G>(s, src, dst, S, d, W, coop); });
+  for (size_t len = NT; len > (size_t)W; len >>= 1)  // sum_k T_k = sum_b b A_b
+    step([&](Xyzz<F> *dst) { launch_pair_step<G>(s, src, dst, len / 2, coop); });
   hipLaunchKernelGGL(k_finalize<G>, dim3(nblk(W, 64)), dim3(64), 0, s, src, fin.as<uint64_t>(), W);
   MSM_HIP_CHECK(hipGetLastError());
 }
-template <int G>
-void ScanReducer<G>::read(hipStream_t s, int W, std::vector<hfp::Jac<HF>> &out) {
-  out.resize(W);
-  MSM_HIP_CHECK(hipMemcpyAsync(out.data(), fin.p, (size_t)W * sizeof(hfp::Jac<HF>), hipMemcpyDeviceToHost, s));
-  MSM_HIP_CHECK(hipStreamSynchronize(s));
-}
 template struct ScanReducer<MSM_GROUP>;
 
-// ---------------------------------------------------------- reduction plan --
-// sum_i w_i S_i = sum_u u L_u + 2^s sum_v v H_v  with u = w_i mod 2^s,
-// v = w_i >> s, L_u = sum_{i: low(w_i) = u} S_i, H_v = sum_{i: high(w_i) = v} S_i.
-// L and H are segment sums over one list of bucket indices (level 0: chunks of
-// <= 8 within a segment; then pairwise levels until one partial per segment;
-// then a dense scatter into 2 windows of 2^s slots), followed by the dense
-// 2-window ScanReducer and a 2^s Horner step on the host.
+// -------------------------------------------------------- weighted reducer --
+// the plan (reduce_plan.hpp) and its tables on the device
 template <int G>
 void WeightedReducer<G>::plan(const std::vector<uint32_t> &w, const std::vector<uint32_t> &win, int nwin, int c0) {
-  typedef typename FieldOf<G>::F F;
-  if (nwin < 1 || (!win.empty() && win.size() != w.size())) throw std::runtime_error("WeightedReducer: bad windows");
-  bsize_ = w.size();
-  nwin_ = nwin;
-  starts_.clear();
-  nout_.clear();
-  uint32_t maxw = 0;
-  for (uint32_t x : w) maxw = std::max(maxw, x);
-  int bits = 0;
-  while (bits < 32 && ((uint64_t)1 << bits) <= maxw) ++bits;
-  sbits_ = std::max(1, (bits + 1) / 2);
-  const uint32_t S = 1u << sbits_;
-  // dense slot layout: window ww -> [L block (2 ww) S | H block (2 ww + 1) S]
-  std::vector<std::vector<uint32_t>> byv((size_t)nwin * S), byu((size_t)nwin * S);
-  for (size_t i = 0; i < w.size(); ++i) {
-    const size_t ww = win.empty() ? 0 : win[i];
-    if (ww >= (size_t)nwin) throw std::runtime_error("WeightedReducer: window out of range");
-    uint32_t v = w[i] >> sbits_, u = w[i] & (S - 1);
-    if (v) byv[ww * S + v].push_back((uint32_t)i);
-    if (u) byu[ww * S + u].push_back((uint32_t)i);
-  }
-  std::vector<uint32_t> idx, seg;
-  for (int ww = 0; ww < nwin; ++ww) {
-    for (uint32_t v = 1; v < S; ++v)
-      for (uint32_t i : byv[(size_t)ww * S + v]) idx.push_back(i), seg.push_back((2 * ww + 1) * S + v - 1);
-    for (uint32_t u = 1; u < S; ++u)
-      for (uint32_t i : byu[(size_t)ww * S + u]) idx.push_back(i), seg.push_back(2 * ww * S + u - 1);
-  }
-  // level 0 + pairwise levels
-  std::vector<uint32_t> cur_seg = seg;
-  // Level-0 chunk length: a chunk of C items is C - 1 dependent adds in one
-  // lane.  Large plans keep 8 (few lanes per item, fewest levels); small ones
-  // (a few hundred thousand items: plain Pippenger at 2^16, CHES shards of
-  // 2^17..2^19) would leave the chip < 1 wave per SIMD deep with 7-add chains
-  // (the 2^16 level 0 ran 103 us for 311 K adds, profiles/archive_r01_r04.txt (r04_fixed_cost.txt)),
-  // so they take 4 or 2 and one or two more (tail) levels.  The adds are the
-  // same in total (items - segments); MSM_L0_CHUNK=<2..64> overrides.
   static const int C0env = [] {
     const char *e = getenv("MSM_L0_CHUNK");  // A/B knob: level-0 chunk length
     return e ? std::max(2, std::min(64, atoi(e))) : 0;
   }();
-  const size_t lane_items = idx.size() * (G == 2 ? 2 : 1);  // G2 segment sums run on lane pairs
-  int C = C0env ? C0env : c0 ? c0 : lane_items >= ((size_t)3 << 19) ? 8 : lane_items >= ((size_t)600 << 10) ? 4 : 2;
-  c0_ = C;
-  while (true) {
-    std::vector<uint32_t> st, nseg;
-    size_t k = 0;
-    while (k < cur_seg.size()) {
-      st.push_back((uint32_t)k);
-      nseg.push_back(cur_seg[k]);
-      size_t e = k + 1;
-      while (e < cur_seg.size() && e - k < (size_t)C && cur_seg[e] == cur_seg[k]) ++e;
-      k = e;
-    }
-    st.push_back((uint32_t)cur_seg.size());
-    bool first = starts_.empty();
-    if (!first && nseg.size() == cur_seg.size()) break;  // nothing merged: one partial per segment
-    starts_.emplace_back();
-    starts_.back().ensure(st.size() * 4);
-    MSM_HIP_CHECK(hipMemcpy(starts_.back().p, st.data(), st.size() * 4, hipMemcpyHostToDevice));
-    nout_.push_back(nseg.size());
-    cur_seg.swap(nseg);
-    C = 2;
-    if (cur_seg.empty()) break;
-  }
-  // bit phase (sync tail of one-window plans): segment (block, j) over the
-  // final partials p of block = cur_seg[p] / S whose value cur_seg[p] % S + 1
-  // has bit j; chunks of 8, pairwise levels, then a scatter to 2 s slots
-  std::vector<uint32_t> bidx;
-  bits_ = nwin == 1;
-  bstarts_.clear();
-  bnout_.clear();
-  if (bits_) {
-    const uint32_t NB2 = 2u * (uint32_t)nwin * (uint32_t)sbits_;
-    std::vector<uint32_t> bseg;
-    for (uint32_t bs = 0; bs < NB2; ++bs) {
-      const uint32_t blk = bs / (uint32_t)sbits_, j = bs % (uint32_t)sbits_;
-      for (size_t q = 0; q < cur_seg.size(); ++q)
-        if (cur_seg[q] / S == blk && (((cur_seg[q] % S) + 1) >> j & 1u)) bidx.push_back((uint32_t)q), bseg.push_back(bs);
-    }
-    int Cb = 2;  // pairwise from the first level: the tail is latency-bound (a chunk of 8 is 7 serial adds in one lane)
-    while (!bseg.empty()) {
-      std::vector<uint32_t> st, nseg;
-      size_t k = 0;
-      while (k < bseg.size()) {
-        st.push_back((uint32_t)k);
-        nseg.push_back(bseg[k]);
-        size_t e = k + 1;
-        while (e < bseg.size() && e - k < (size_t)Cb && bseg[e] == bseg[k]) ++e;
-        k = e;
-      }
-      st.push_back((uint32_t)bseg.size());
-      if (!bnout_.empty() && nseg.size() == bseg.size()) break;
-      bstarts_.emplace_back();
-      bstarts_.back().ensure(st.size() * 4);
-      MSM_HIP_CHECK(hipMemcpy(bstarts_.back().p, st.data(), st.size() * 4, hipMemcpyHostToDevice));
-      bnout_.push_back(nseg.size());
-      bseg.swap(nseg);
-      Cb = 2;
-    }
-    std::vector<uint32_t> bdst(NB2 + 1, 0), bperm;
-    std::vector<int> bat(NB2, -1);
-    for (size_t k = 0; k < bseg.size(); ++k) bat[bseg[k]] = (int)k;
-    for (uint32_t sl = 0; sl < NB2; ++sl) {
-      bdst[sl] = (uint32_t)bperm.size();
-      if (bat[sl] >= 0) bperm.push_back((uint32_t)bat[sl]);
-    }
-    bdst[NB2] = (uint32_t)bperm.size();
-    bstarts_.emplace_back();
-    bstarts_.back().ensure(bdst.size() * 4);
-    MSM_HIP_CHECK(hipMemcpy(bstarts_.back().p, bdst.data(), bdst.size() * 4, hipMemcpyHostToDevice));
-    bnout_.push_back(NB2);
-    bidx.insert(bidx.end(), bperm.begin(), bperm.end());
-    bperm_off_ = bidx.size() - bperm.size();
-    bfin_.ensure((size_t)NB2 * 144 * G);
-  }
-  // dense scatter: slot -> its single partial (or empty), via a permutation
-  const size_t NS = (size_t)2 * nwin * S;
-  std::vector<uint32_t> dst(NS + 1, 0), perm;
-  std::vector<int> at(NS, -1);
-  for (size_t k = 0; k < cur_seg.size(); ++k) at[cur_seg[k]] = (int)k;
-  for (size_t sl = 0; sl < NS; ++sl) {
-    dst[sl] = (uint32_t)perm.size();
-    if (at[sl] >= 0) perm.push_back((uint32_t)at[sl]);
-  }
-  dst[NS] = (uint32_t)perm.size();
-  starts_.emplace_back();
-  starts_.back().ensure(dst.size() * 4);
-  MSM_HIP_CHECK(hipMemcpy(starts_.back().p, dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
-  nout_.push_back(NS);
-  std::vector<uint32_t> all = idx;  // [level-0 item list | final permutation | bit phase items | bit permutation]
-  all.insert(all.end(), perm.begin(), perm.end());
-  final_perm_off_ = idx.size();
-  bidx_off_ = all.size();
-  bperm_off_ += bidx_off_;
-  all.insert(all.end(), bidx.begin(), bidx.end());
-  idx_.ensure(std::max<size_t>(all.size(), 1) * 4);
-  if (!all.empty()) MSM_HIP_CHECK(hipMemcpy(idx_.p, all.data(), all.size() * 4, hipMemcpyHostToDevice));
-  maxp_ = 1;
-  for (size_t l = 0; l + 1 < nout_.size(); ++l) maxp_ = std::max(maxp_, nout_[l]);
-  for (size_t l = 0; l + 1 < bnout_.size(); ++l) maxp_ = std::max(maxp_, bnout_[l]);  // bit phase levels
-  maxp1_ = 1;  // batch group tails: level l writes part_[l & 1]; the odd levels are at most half of level 0
-  for (size_t l = 1; l + 1 < nout_.size(); l += 2) maxp1_ = std::max(maxp1_, nout_[l]);
-  // (the group bit tail, launch_tail_group_bits, alternates its levels over both
-  // part_ buffers: every bit level fits either)
-  for (size_t l = 0; l + 1 < bnout_.size(); ++l) maxp1_ = std::max(maxp1_, bnout_[l]);
+  plan_ = ReducePlan::build(w, win, nwin, C0env ? C0env : c0, G == 2 ? 2 : 1);
+  steps_[kEndDense] = plan_.steps(kEndDense);
+  steps_[kEndBits] = has_bit_tail() ? plan_.steps(kEndBits) : std::vector<ReduceStep>();
+  starts_.clear();
+  starts_.resize(plan_.levels());
+  auto upload = [](DevBuf &d, const std::vector<uint32_t> &v) {
+    d.ensure(std::max<size_t>(v.size(), 1) * 4);
+    if (!v.empty()) MSM_HIP_CHECK(hipMemcpy(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+  };
+  // the segment phase's scatter after the bit phase
+  const int L = (int)plan_.seg.size(), LT = (int)plan_.levels();
+  for (int t = 0; t < LT; ++t)
+    if (t != L - 1) upload(starts_[t], plan_.level(t).starts);
+  upload(starts_[L - 1], plan_.level(L - 1).starts);
+  upload(idx_, plan_.items);
   for (int st = 0; st < NSETS; ++st) {  // a new plan: sets are (re)sized on their next use
     part_[st][0].release();
     part_[st][1].release();
     dense_buf_[st].release();
   }
-  ensure_set(0);
 }
 
 template <int G>
-void WeightedReducer<G>::ensure_set(int set) {
-  typedef typename FieldOf<G>::F F;
-  if (set < 0 || set >= NSETS) throw std::runtime_error("WeightedReducer: bad buffer set");
-  part_[set][0].ensure(maxp_ * sizeof(Xyzz<F>));
-  part_[set][1].ensure(maxp_ * sizeof(Xyzz<F>));
-  dense_buf_[set].ensure((size_t)2 * nwin_ * ((size_t)1 << sbits_) * sizeof(Xyzz<F>));
-}
-
-template <int G>
-void WeightedReducer<G>::launch_head(hipStream_t s, const void *Sbuf, int set) {
-  typedef typename FieldOf<G>::F F;
-  ensure_set(set);
-  const size_t L = nout_.size();
-  const Xyzz<F> *src = reinterpret_cast<const Xyzz<F> *>(Sbuf);
-  Xyzz<F> *dst = L == 1 ? dense_buf_[set].as<Xyzz<F>>() : part_[set][0].as<Xyzz<F>>();
-  const uint32_t *ix = L == 1 ? idx_.as<uint32_t>() + final_perm_off_ : idx_.as<uint32_t>();
-  launch_segsum<G>(s, src, ix, starts_[0].as<uint32_t>(), dst, nout_[0]);
-  MSM_HIP_CHECK(hipGetLastError());
-}
-
-template <int G>
-void WeightedReducer<G>::launch_tail(hipStream_t s, int set, bool coop) {
-  typedef typename FieldOf<G>::F F;
-  const size_t L = nout_.size();
-  const Xyzz<F> *src = part_[set][0].as<Xyzz<F>>();
-  if (bits_ && L >= 2) {
-    // phase-1 levels 1 .. L-2 (level L-1 is the dense scatter, not used here),
-    // then the bit phase: its level 0 reads the final partials through the
-    // bit item list, later levels are contiguous, the last scatters to 2 s slots
-    int cur = 0;
-    auto segsum = [&](const Xyzz<F> *a, const uint32_t *ix, const uint32_t *st, Xyzz<F> *d, size_t nout) {
-      if (!nout) return;
-      launch_segsum_tail<G>(s, a, ix, st, d, nout, coop);
-      MSM_HIP_CHECK(hipGetLastError());
-    };
-    for (size_t l = 1; l + 1 < L; ++l) {
-      Xyzz<F> *dst = part_[set][l & 1].as<Xyzz<F>>();
-      segsum(src, nullptr, starts_[l].as<uint32_t>(), dst, nout_[l]);
-      src = dst;
-      cur = (int)(l & 1);
-    }
-    const size_t LB = bnout_.size();
-    for (size_t l = 0; l < LB; ++l) {
-      const bool last = l + 1 == LB;
-      Xyzz<F> *dst = last ? dense_buf_[set].as<Xyzz<F>>() : part_[set][cur ^ 1].as<Xyzz<F>>();
-      const uint32_t *ix = l == 0 ? idx_.as<uint32_t>() + bidx_off_ : last ? idx_.as<uint32_t>() + bperm_off_ : nullptr;
-      segsum(src, ix, bstarts_[l].as<uint32_t>(), dst, bnout_[l]);
-      src = dst;
-      cur ^= 1;
-    }
-    hipLaunchKernelGGL(k_finalize<G>, dim3(nblk(bit_slots(), 64)), dim3(64), 0, s, src, bfin_.as<uint64_t>(),
-                       (int)bit_slots());
-    MSM_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  for (size_t l = 1; l < L; ++l) {
-    const bool last = l + 1 == L;
-    Xyzz<F> *dst = last ? dense_buf_[set].as<Xyzz<F>>() : part_[set][l & 1].as<Xyzz<F>>();
-    const uint32_t *ix = last ? idx_.as<uint32_t>() + final_perm_off_ : nullptr;
-    if (nout_[l]) launch_segsum_tail<G>(s, src, ix, starts_[l].as<uint32_t>(), dst, nout_[l], coop);
-    MSM_HIP_CHECK(hipGetLastError());
-    src = dst;
-  }
-  dense_[set].launch(s, dense_buf_[set].p, 2 * nwin_, 1 << sbits_, coop);
-}
-
-template <int G>
-void WeightedReducer<G>::ensure_group(int set, int nmsm) {
+void WeightedReducer<G>::ensure(int set, int nmsm) {
   typedef typename FieldOf<G>::F F;
   if (set < 0 || set >= NSETS || nmsm < 1) throw std::runtime_error("WeightedReducer: bad group");
-  part_[set][0].ensure((size_t)nmsm * maxp_ * sizeof(Xyzz<F>));
-  part_[set][1].ensure((size_t)nmsm * maxp1_ * sizeof(Xyzz<F>));
-  if (bits_) bgfin_[set].ensure((size_t)nmsm * bit_bytes());
-  dense_buf_[set].ensure((size_t)nmsm * dense_slots() * sizeof(Xyzz<F>));
-  const size_t NT = (size_t)nmsm * dense_slots();  // ScanReducer::launch's buffers for W = 2 nwin nmsm
+  part_[set][0].ensure(plan_.elems(kRedPart0, nmsm) * sizeof(Xyzz<F>));
+  part_[set][1].ensure(plan_.elems(kRedPart1, nmsm) * sizeof(Xyzz<F>));
+  if (has_bit_tail()) bgfin_[set].ensure((size_t)nmsm * bit_bytes());
+  const size_t NT = plan_.elems(kRedDense, nmsm);  // also ScanReducer::launch's buffers for W = 2 nwin nmsm
+  dense_buf_[set].ensure(NT * sizeof(Xyzz<F>));
   dense_[set].buf[0].ensure(NT * sizeof(Xyzz<F>));
   dense_[set].buf[1].ensure(NT * sizeof(Xyzz<F>));
   dense_[set].fin.ensure((size_t)nmsm * out_bytes());
 }
 
 template <int G>
-typename WeightedReducer<G>::HeadArgs WeightedReducer<G>::head_args(int set, int slot) {
+void WeightedReducer<G>::head(hipStream_t s, const void *Sbuf, size_t sstride, int set, int slot0, int nmsm) {
   typedef typename FieldOf<G>::F F;
-  const bool only = nout_.size() == 1;  // level 0 is also the last level
-  Xyzz<F> *dst = only ? dense_buf_[set].as<Xyzz<F>>() + (size_t)slot * dense_slots()
-                      : part_[set][0].as<Xyzz<F>>() + (size_t)slot * maxp_;
-  const uint32_t *ix = only ? idx_.as<uint32_t>() + final_perm_off_ : idx_.as<uint32_t>();
-  return HeadArgs{ix, starts_[0].as<uint32_t>(), dst, nout_[0]};
-}
-
-template <int G>
-void WeightedReducer<G>::launch_head_slot(hipStream_t s, const void *Sbuf, int set, int slot) {
-  typedef typename FieldOf<G>::F F;
-  const HeadArgs a = head_args(set, slot);
-  launch_segsum<G>(s, reinterpret_cast<const Xyzz<F> *>(Sbuf), a.idx, a.starts, static_cast<Xyzz<F> *>(a.dst),
-                   a.nout);
+  const ReduceStep &st = steps_[kEndDense].front();  // level 0 is the same in either ending
+  launch_segsum<G>(s, reinterpret_cast<const Xyzz<F> *>(Sbuf), idx_.as<uint32_t>() + st.items,
+                   starts_[st.level].template as<uint32_t>(),
+                   buf(set, st.dst).template as<Xyzz<F>>() + (size_t)slot0 * st.dstride, plan_.level(st.level).nout, nmsm,
+                   sstride, st.dstride);
   MSM_HIP_CHECK(hipGetLastError());
 }
 
 template <int G>
-void WeightedReducer<G>::launch_head_slots(hipStream_t s, const void *Sbuf, size_t sstride, int set, int slot0,
-                                           int nmsm) {
+void WeightedReducer<G>::tail(hipStream_t s, int set, int nmsm, ReduceEnding end, bool coop) {
   typedef typename FieldOf<G>::F F;
-  const bool only = nout_.size() == 1;  // level 0 is also the last level
-  const HeadArgs a = head_args(set, slot0);
-  launch_segsum<G>(s, reinterpret_cast<const Xyzz<F> *>(Sbuf), a.idx, a.starts, static_cast<Xyzz<F> *>(a.dst), a.nout,
-                   nmsm, sstride, only ? dense_slots() : maxp_);
-  MSM_HIP_CHECK(hipGetLastError());
-}
-
-template <int G>
-void WeightedReducer<G>::launch_tail_group(hipStream_t s, int set, int nmsm, bool coop) {
-  typedef typename FieldOf<G>::F F;
-  const size_t L = nout_.size();
-  const Xyzz<F> *src = part_[set][0].as<Xyzz<F>>();
-  for (size_t l = 1; l < L; ++l) {
-    const bool last = l + 1 == L;
-    Xyzz<F> *dst = last ? dense_buf_[set].as<Xyzz<F>>() : part_[set][l & 1].as<Xyzz<F>>();
-    const uint32_t *ix = last ? idx_.as<uint32_t>() + final_perm_off_ : nullptr;
-    const size_t sstride = (l & 1) ? maxp_ : maxp1_;  // level l - 1 wrote part_[(l - 1) & 1]
-    // coop (the batch's last group: nothing left to overlap): the narrow levels
-    // over 4 waves per add
-    launch_segsum_tail<G>(s, src, ix, starts_[l].as<uint32_t>(), dst, nout_[l], coop, nmsm, sstride,
-                          last ? dense_slots() : (l & 1) ? maxp1_ : maxp_);
+  const std::vector<ReduceStep> &steps = steps_[end];
+  if (steps.empty()) throw std::runtime_error("WeightedReducer: no bit tail in this plan");
+  for (size_t k = 1; k < steps.size(); ++k) {
+    const ReduceStep &st = steps[k];
+    const size_t nout = plan_.level(st.level).nout;
+    if (!nout) continue;
+    launch_segsum_tail<G>(s, buf(set, st.src).template as<Xyzz<F>>(),
+                          st.items == kNoItems ? nullptr : idx_.as<uint32_t>() + st.items,
+                          starts_[st.level].template as<uint32_t>(), buf(set, st.dst).template as<Xyzz<F>>(), nout, coop,
+                          nmsm, st.sstride, st.dstride);
     MSM_HIP_CHECK(hipGetLastError());
-    src = dst;
   }
-  dense_[set].launch(s, dense_buf_[set].p, 2 * nwin_ * nmsm, 1 << sbits_, coop);
-}
-
-// The group tail ending in bit sums (one-window plans): the segment levels,
-// then per MSM the 2 s bit sums B_j (the bit phase of launch_tail, every level
-// one launch for the group), finalized to nmsm x 2 s Jacobians; the host
-// combines T = sum_j 2^j B_j (combine_bits).  ~10 levels instead of the 2 s of
-// the dense stage: for the batch's LAST group, whose tail runs after the last
-// accumulation with the chip otherwise idle (Ches::run_jobs).
-template <int G>
-void WeightedReducer<G>::launch_tail_group_bits(hipStream_t s, int set, int nmsm, bool coop) {
-  typedef typename FieldOf<G>::F F;
-  const size_t L = nout_.size(), LB = bnout_.size();
-  if (!has_bit_tail()) throw std::runtime_error("WeightedReducer: no bit tail in this plan");
-  const Xyzz<F> *src = part_[set][0].as<Xyzz<F>>();
-  size_t sstride = maxp_;
-  int cur = 0;
-  for (size_t l = 1; l + 1 < L; ++l) {  // segment levels 1 .. L-2 (L-1 is the dense scatter)
-    Xyzz<F> *dst = part_[set][l & 1].as<Xyzz<F>>();
-    const size_t dstride = (l & 1) ? maxp1_ : maxp_;
-    if (nout_[l]) launch_segsum_tail<G>(s, src, nullptr, starts_[l].as<uint32_t>(), dst, nout_[l], coop, nmsm, sstride,
-                                        dstride);
+  if (end == kEndDense) {
+    dense_[set].launch(s, dense_buf_[set].p, 2 * plan_.nwin * nmsm, 1 << plan_.sbits, coop);
+  } else {  // nmsm x 2 s bit sums to Jacobians; the host combines T = sum_j 2^j B_j (combine_bits)
+    const int W = (int)((size_t)nmsm * plan_.bit_slots());
+    hipLaunchKernelGGL(k_finalize<G>, dim3(nblk((size_t)W, 64)), dim3(64), 0, s, dense_buf_[set].as<Xyzz<F>>(),
+                       bgfin_[set].as<uint64_t>(), W);
     MSM_HIP_CHECK(hipGetLastError());
-    src = dst;
-    sstride = dstride;
-    cur = (int)(l & 1);
   }
-  for (size_t l = 0; l < LB; ++l) {
-    const bool last = l + 1 == LB;
-    const int nb = cur ^ 1;
-    Xyzz<F> *dst = last ? dense_buf_[set].as<Xyzz<F>>() : part_[set][nb].as<Xyzz<F>>();
-    const size_t dstride = last ? bit_slots() : nb ? maxp1_ : maxp_;
-    const uint32_t *ix = l == 0 ? idx_.as<uint32_t>() + bidx_off_ : last ? idx_.as<uint32_t>() + bperm_off_ : nullptr;
-    if (bnout_[l])
-      launch_segsum_tail<G>(s, src, ix, bstarts_[l].as<uint32_t>(), dst, bnout_[l], coop, nmsm, sstride, dstride);
-    MSM_HIP_CHECK(hipGetLastError());
-    src = dst;
-    sstride = dstride;
-    cur = nb;
-  }
-  const int W = (int)((size_t)nmsm * bit_slots());
-  hipLaunchKernelGGL(k_finalize<G>, dim3(nblk((size_t)W, 64)), dim3(64), 0, s, src, bgfin_[set].as<uint64_t>(), W);
-  MSM_HIP_CHECK(hipGetLastError());
 }
 
 template <int G>
-void WeightedReducer<G>::copy_out_group_bits(hipStream_t s, int set, int nmsm, void *host) {
-  MSM_HIP_CHECK(hipMemcpyAsync(host, bgfin_[set].p, (size_t)nmsm * bit_bytes(), hipMemcpyDefault, s));
-}
-
-// window 0's sum_b b S_b from its 2 s bit sums (bit j of the weight: low half
-// block j < s, high half s + j): Horner from the top bit, as read_windows
-template <int G>
-hfp::Jac<typename HostField<G>::F> WeightedReducer<G>::combine_bits(const void *host) const {
-  const hfp::Jac<HF> *B = reinterpret_cast<const hfp::Jac<HF> *>(host);
-  const hfp::Jac<HF> *lo = B, *hi = B + sbits_;
-  hfp::Jac<HF> acc = hi[sbits_ - 1];
-  for (int j = 2 * sbits_ - 2; j >= 0; --j) {
-    acc = hfp::dbl(acc);
-    acc = hfp::addj(acc, j >= sbits_ ? hi[j - sbits_] : lo[j]);
-  }
-  return acc;
-}
-
-template <int G>
-void WeightedReducer<G>::copy_out_group(hipStream_t s, int set, int nmsm, void *host) {
-  // host (read-back) or device (an exchange buffer, ChesMulti's RCCL gather)
-  MSM_HIP_CHECK(hipMemcpyAsync(host, dense_[set].fin.p, (size_t)nmsm * out_bytes(), hipMemcpyDefault, s));
-}
-
-template <int G>
-void WeightedReducer<G>::copy_out(hipStream_t s, int set, void *host) {
-  MSM_HIP_CHECK(hipMemcpyAsync(host, dense_[set].fin.p, out_bytes(), hipMemcpyDeviceToHost, s));
+void WeightedReducer<G>::copy_out(hipStream_t s, int set, int nmsm, ReduceEnding end, void *dst, hipMemcpyKind kind) {
+  const bool bits = end == kEndBits;
+  MSM_HIP_CHECK(hipMemcpyAsync(dst, bits ? bgfin_[set].p : dense_[set].fin.p,
+                               (size_t)nmsm * (bits ? bit_bytes() : out_bytes()), kind, s));
 }
 
 template <int G>
 std::vector<hfp::Jac<typename HostField<G>::F>> WeightedReducer<G>::combine(const void *host) const {
   const hfp::Jac<HF> *T = reinterpret_cast<const hfp::Jac<HF> *>(host);
-  std::vector<hfp::Jac<HF>> out(nwin_);
-  for (int ww = 0; ww < nwin_; ++ww) out[ww] = horner(std::vector<hfp::Jac<HF>>{T[2 * ww], T[2 * ww + 1]}, sbits_);
+  std::vector<hfp::Jac<HF>> out(plan_.nwin);
+  for (int ww = 0; ww < plan_.nwin; ++ww)
+    out[ww] = horner(std::vector<hfp::Jac<HF>>{T[2 * ww], T[2 * ww + 1]}, plan_.sbits);
   return out;
 }
 
+// window 0's sum_b b S_b from its 2 s bit sums (bit j of the weight: low half
+// block j < s, high half s + j): Horner from the top bit
 template <int G>
-std::vector<hfp::Jac<typename HostField<G>::F>> WeightedReducer<G>::read_windows(hipStream_t s) {
-  if (bits_ && nout_.size() >= 2) {  // launch_tail's bit sums: T = sum_j 2^j B_j, Horner from the top bit
-    std::vector<hfp::Jac<HF>> B(bit_slots());
-    MSM_HIP_CHECK(hipMemcpyAsync(B.data(), bfin_.p, bit_slots() * sizeof(hfp::Jac<HF>), hipMemcpyDeviceToHost, s));
-    MSM_HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<hfp::Jac<HF>> out(nwin_);
-    for (int ww = 0; ww < nwin_; ++ww) {
-      // bit j of the window's weight: low half block 2 ww (j < s), high half block 2 ww + 1
-      const hfp::Jac<HF> *lo = &B[(size_t)2 * ww * sbits_], *hi = lo + sbits_;
-      hfp::Jac<HF> acc = hi[sbits_ - 1];
-      for (int j = 2 * sbits_ - 2; j >= 0; --j) {
-        acc = hfp::dbl(acc);
-        acc = hfp::addj(acc, j >= sbits_ ? hi[j - sbits_] : lo[j]);
-      }
-      out[ww] = acc;
-    }
-    return out;
+hfp::Jac<typename HostField<G>::F> WeightedReducer<G>::combine_bits(const void *host) const {
+  const int sbits = plan_.sbits;
+  const hfp::Jac<HF> *B = reinterpret_cast<const hfp::Jac<HF> *>(host);
+  const hfp::Jac<HF> *lo = B, *hi = B + sbits;
+  hfp::Jac<HF> acc = hi[sbits - 1];
+  for (int j = 2 * sbits - 2; j >= 0; --j) {
+    acc = hfp::dbl(acc);
+    acc = hfp::addj(acc, j >= sbits ? hi[j - sbits] : lo[j]);
   }
-  std::vector<uint8_t> host(out_bytes());
-  copy_out(s, 0, host.data());
-  MSM_HIP_CHECK(hipStreamSynchronize(s));
-  return combine(host.data());
+  return acc;
 }
 
 template <int G>
@@ -621,9 +240,9 @@ hfp::Jac<typename HostField<G>::F> WeightedReducer<G>::combine_windows(const voi
   const hfp::Jac<HF> *T = reinterpret_cast<const hfp::Jac<HF> *>(host);
   // terms (exponent, point): L_w at c w, H_w at c w + s; Horner from the top
   std::vector<std::pair<long, int>> terms;
-  for (int ww = 0; ww < nwin_; ++ww) {
+  for (int ww = 0; ww < plan_.nwin; ++ww) {
     terms.emplace_back((long)c * ww, 2 * ww);
-    terms.emplace_back((long)c * ww + sbits_, 2 * ww + 1);
+    terms.emplace_back((long)c * ww + plan_.sbits, 2 * ww + 1);
   }
   std::sort(terms.begin(), terms.end());
   hfp::Jac<HF> acc = T[terms.back().second];
@@ -636,14 +255,22 @@ hfp::Jac<typename HostField<G>::F> WeightedReducer<G>::combine_windows(const voi
   return acc;
 }
 
+// the synchronous reads of set 0 (after launch)
+template <int G>
+std::vector<hfp::Jac<typename HostField<G>::F>> WeightedReducer<G>::read_windows(hipStream_t s) {
+  const ReduceEnding end = sync_ending();
+  std::vector<uint8_t> host(end == kEndBits ? bit_bytes() : out_bytes());
+  copy_out(s, 0, 1, end, host.data(), hipMemcpyDeviceToHost);
+  MSM_HIP_CHECK(hipStreamSynchronize(s));
+  if (end == kEndBits) return {combine_bits(host.data())};  // a one-window plan
+  return combine(host.data());
+}
+
 template <int G>
 hfp::Jac<typename HostField<G>::F> WeightedReducer<G>::read_total(hipStream_t s, int c) {
-  if (bits_ && nout_.size() >= 2) {  // one-window plan ended in bit sums (launch_tail): its T_0 is the total
-    const std::vector<hfp::Jac<HF>> T = read_windows(s);
-    return horner(T, c);
-  }
+  if (sync_ending() == kEndBits) return read_windows(s)[0];  // one window: its T_0 is the total
   std::vector<uint8_t> host(out_bytes());
-  copy_out(s, 0, host.data());
+  copy_out(s, 0, 1, kEndDense, host.data(), hipMemcpyDeviceToHost);
   MSM_HIP_CHECK(hipStreamSynchronize(s));
   return combine_windows(host.data(), c);
 }
@@ -1024,21 +651,19 @@ struct Ches<G>::BatchSink {
   void accumulate_group(int s, size_t g, int gb) {
     e.accumulate_sets(st[s], (int)(g % p.nfr), (int)(p.fgb[g + 1] - p.fgb[g]), gb, job_table(p.fgb[g]));
   }
-  void level0(int s, int bset, int rset, int slot) { red.launch_head_slot(st[s], e.buckets_[bset].p, rset, slot); }
+  void level0(int s, int bset, int rset, int slot) {
+    red.head(st[s], e.buckets_[bset].p, e.bucket_count(), rset, slot, 1);
+  }
   void level0_group(int s, int gb, size_t off, int rset, int slot0, int m) {
     const size_t NB = e.bucket_count();
-    red.launch_head_slots(st[s], e.gbuckets_[gb].template as<uint8_t>() + off * NB * sizeof(Xyzz<typename FieldOf<G>::F>),
-                          NB, rset, slot0, m);
+    red.head(st[s], e.gbuckets_[gb].template as<uint8_t>() + off * NB * sizeof(Xyzz<typename FieldOf<G>::F>), NB, rset,
+             slot0, m);
   }
   // the dense stage into the read-back slots, or (the last group, bit_tail) the bit phase into host_bits_
   void tail(int s, int rset, size_t first, size_t m, bool last) {
-    if (p.bit_tail && last) {
-      red.launch_tail_group_bits(st[s], rset, (int)m, p.tail_coop);
-      red.copy_out_group_bits(st[s], rset, (int)m, e.host_bits_);
-    } else {
-      red.launch_tail_group(st[s], rset, (int)m, p.tail_coop && last);
-      red.copy_out_group(st[s], rset, (int)m, out_base + first * red.out_bytes());
-    }
+    const ReduceEnding end = p.bit_tail && last ? kEndBits : kEndDense;
+    red.tail(st[s], rset, (int)m, end, p.tail_coop && last);
+    red.copy_out(st[s], rset, (int)m, end, end == kEndBits ? e.host_bits_ : out_base + first * red.out_bytes());
   }
   void combine(size_t, size_t) {}
   void prof_begin(int s, size_t k) {
@@ -1102,7 +727,7 @@ void Ches<G>::batch_buffers(const BatchPlan &p, hipStream_t s, size_t stride) {
   ensure_pinned(host_bits_, host_bits_bytes_, p.bits_need, p.bits_alloc);
   for (int b = 0; b < p.bucket_sets; ++b) (p.sched == kAccGroups ? gbuckets_ : buckets_)[b].ensure(p.bucket_set_bytes);
   if ((int)fs_.size() < p.nfr) fs_.resize(p.nfr);
-  for (int t = 0; t < p.nred; ++t) batch_red_->ensure_group(t, (int)p.group_max);
+  for (int t = 0; t < p.nred; ++t) batch_red_->ensure(t, (int)p.group_max);
   // front sets sized for a whole front group (the sort's scan scratch too): run
   // one sort of fg_max sets per set before the loop if they are not yet sized
   // (fg_max dummy sets of all-zero scalars, outside the batch timing)

@@ -330,11 +330,11 @@ struct Pippenger<G>::BatchSink {
   }
   void level0(int, int, int, int) {}
   void level0_group(int s, int gb, size_t off, int rset, int slot0, int m) {
-    red.launch_head_slots(st[s], e.gbuckets_[gb].template as<uint8_t>() + off * NT * sizeof(Xyzz<F>), NT, rset, slot0, m);
+    red.head(st[s], e.gbuckets_[gb].template as<uint8_t>() + off * NT * sizeof(Xyzz<F>), NT, rset, slot0, m);
   }
   void tail(int s, int rset, size_t first, size_t m, bool last) {
-    red.launch_tail_group(st[s], rset, (int)m, p.tail_coop && last);
-    red.copy_out_group(st[s], rset, (int)m, (uint8_t *)e.host_out_ + first * red.out_bytes());
+    red.tail(st[s], rset, (int)m, kEndDense, p.tail_coop && last);
+    red.copy_out(st[s], rset, (int)m, kEndDense, (uint8_t *)e.host_out_ + first * red.out_bytes());
   }
   void combine(size_t first, size_t m) {  // spread over the host worker threads
     WorkerPool::get().parallel_for(m, [&](size_t i) {
@@ -373,7 +373,7 @@ void Pippenger<G>::batch_buffers(const BatchPlan &p, hipStream_t s, const uint8_
   }
   for (ChesFrontSet &f : fs_) f.sort.fine_bt = p.fine_bt;
   for (DevBuf &b : gbuckets_) b.ensure(p.fg_max * NT * sizeof(Xyzz<F>));
-  for (int t = 0; t < p.nred; ++t) batch_red_->ensure_group(t, (int)p.group_max);
+  for (int t = 0; t < p.nred; ++t) batch_red_->ensure(t, (int)p.group_max);
   for (int f = 0; f < p.nfr; ++f)
     if (fs_[f].sorted.bytes < (size_t)W * n_ * p.fg_max * 4 + 64)
       front(s, d_scalars, stride, nbits, nullptr, fs_[f], (int)p.fg_max, 0);

@@ -12,7 +12,9 @@
 
 #include "acc_sched.hpp"
 #include "batch_plan.hpp"
+#include "ches_setup.hpp"
 #include "host_fp.hpp"
+#include "reduce_plan.hpp"
 
 #define MSM_HIP_CHECK(x)                                                                           \
   do {                                                                                            \
@@ -133,20 +135,7 @@ hfp::Jac<HF> horner(const std::vector<hfp::Jac<HF>> &T, int c) {
 // ---------------------------------------------------------------------------
 // CHES "nh + q/5" bucket-set method (ches.hip)
 // ---------------------------------------------------------------------------
-// parameters of ref ches_config_files/config_file_n_exp_*.h
-struct ChesParams {
-  int n_exp, beta, q_exp, h, a_h, d_max, b_size, q_exp_bgmw, h_bgmw;
-};
-bool ches_params_for(int n_exp, int beta, ChesParams *out);
-// bucket set B of ref auxiliaryfunc.h:257-288 (ascending)
-std::vector<int> ches_bucket_set(int q, int a_h);
-// packed digit hash (ches_kernels.hpp layout) of ref main_p1.cpp:140-152, q+1 entries
-std::vector<uint32_t> ches_digit_hash(const std::vector<int> &B, int q);
-// The same map in the compact device form (ches_kernels.hpp "digit code"):
-// a 4-bit code per digit value, 8 per word, (q >> 3) + 2 words, and the rank
-// table {membership bits, prefix count} per 32 values of [0, max B].  Throws if
-// some H[d] is not (m, (alpha ? q - d : d) / m, alpha).
-void ches_digit_code(const std::vector<int> &B, int q, std::vector<uint32_t> &code, std::vector<uint32_t> &rank);
+// parameters, bucket set B, digit hash and digit code: ches_setup.hpp
 
 // Low-depth dense reduction: for each of W windows of S buckets (A[w*S + b-1]
 // holds bucket value b, S a power of two), T_w = sum_b b A_b computed as the sum
@@ -162,111 +151,84 @@ struct ScanReducer {
   // waves (coop.hpp; shortest latency when the GPU is otherwise idle) instead of
   // one add per lane (least resource time beside other kernels)
   void launch(hipStream_t s, const void *A, int W, int S, bool coop = true);
-  void read(hipStream_t s, int W, std::vector<hfp::Jac<HF>> &out);
 };
 
 // sum_i w[i] * S_i for arbitrary non-negative bucket weights w (w = 0: bucket
 // ignored) over device xyzz buckets S (replaces ref multi_scalar.c:301-321).
 // Two regroupings by the low and high halves of w[i] (2 xyzz adds per bucket),
-// then a dense 2-window ScanReducer and one 2^s Horner step on the host.  The
-// plan depends only on w and is built once.  Two independent buffer sets let
-// the latency-bound tail of one MSM (launch_tail, on a second stream) overlap
-// the next MSM's digits/sort/accumulation/level-0 (launch_head).
+// then a dense 2-window ScanReducer and one 2^s Horner step on the host, or
+// (one-window plans) 2 s bit sums and a 2 s-step Horner.  The plan
+// (reduce_plan.hpp) depends only on w and is built once.  NSETS independent
+// buffer sets let the latency-bound tail of one group of MSMs (tail, on a
+// second stream) overlap the next MSMs' digits/sort/accumulation/level 0 (head).
+// The plan is the same for every MSM of a batch, so nmsm MSMs share a buffer
+// set -- each MSM's level 0 writes its own slot, then ONE launch per tail level
+// reduces all slots together (~35 tail launches per group instead of per MSM:
+// every launch beside an accumulation costs it time).
 template <int G>
 class WeightedReducer {
  public:
   typedef typename HostField<G>::F HF;
   static constexpr int NSETS = 4;  // buffer sets, allocated on first use (batch reduction groups rotate over them)
   // win[i] in [0, nwin): the window of bucket i (empty = all in window 0)
-  // c0: level-0 chunk length (0: by plan size, see plan())
+  // c0: level-0 chunk length (0: by plan size, ReducePlan::build); MSM_L0_CHUNK=<2..64> overrides
   void plan(const std::vector<uint32_t> &w, const std::vector<uint32_t> &win, int nwin, int c0 = 0);
   void plan(const std::vector<uint32_t> &w, int c0 = 0) { plan(w, {}, 1, c0); }
-  int level0_chunk() const { return c0_; }
-  void launch_head(hipStream_t s, const void *S, int set);  // level 0 (reads S = xyzz[w.size()])
-  // levels >= 1, dense, finalize; coop: see ScanReducer::launch
-  void launch_tail(hipStream_t s, int set, bool coop = true);
-  void launch(hipStream_t s, const void *S) {
-    launch_head(s, S, 0);
-    launch_tail(s, 0);
-  }
-  size_t out_bytes() const { return (size_t)2 * nwin_ * 144 * G; }
-  void copy_out(hipStream_t s, int set, void *host);               // async D2H of out_bytes()
-  std::vector<hfp::Jac<HF>> combine(const void *host) const;        // per-window sums
+  int level0_chunk() const { return plan_.c0; }
+  // size buffer set `set` for nmsm MSMs, either ending (head and tail allocate nothing)
+  void ensure(int set, int nmsm);
+  // level 0 of nmsm consecutive MSMs (slots slot0 .. slot0 + nmsm - 1 of set
+  // `set`) in one launch; MSM j's buckets (xyzz[size()]) at S + j sstride points
+  void head(hipStream_t s, const void *S, size_t sstride, int set, int slot0, int nmsm);
+  // levels >= 1 of slots 0 .. nmsm - 1, then the dense stage and finalize
+  // (kEndDense) or the bit phase and finalize (kEndBits: has_bit_tail(), ~10
+  // levels instead of the dense stage's 2 s, for a tail that runs with the chip
+  // otherwise idle).  coop: narrow levels run their adds over 4 waves each
+  // (coop.hpp; shortest latency when nothing else runs) instead of one per lane
+  void tail(hipStream_t s, int set, int nmsm, ReduceEnding end, bool coop);
+  // async copy of nmsm * out_bytes() (kEndDense) or nmsm * bit_bytes() to dst:
+  // host memory, or device memory (an exchange buffer, ChesMulti's RCCL gather)
+  void copy_out(hipStream_t s, int set, int nmsm, ReduceEnding end, void *dst, hipMemcpyKind kind = hipMemcpyDefault);
+  size_t out_bytes() const { return (size_t)2 * plan_.nwin * 144 * G; }
+  size_t bit_bytes() const { return plan_.bit_slots() * 144 * G; }
+  bool has_bit_tail() const { return plan_.has_bit_tail(); }
+  std::vector<hfp::Jac<HF>> combine(const void *host) const;  // per-window sums of one MSM's out_bytes()
+  // window 0's sum of one MSM's bit_bytes() = combine(...)[0]
+  hfp::Jac<HF> combine_bits(const void *host) const;
   // sum_w 2^(c w) T_w of a copied-out result in ONE Horner pass over the 2 nwin
   // terms L_w (exponent c w) and H_w (c w + s): (nwin - 1) c + s doublings
   // instead of nwin s + (nwin - 1) c (combine, then horner over the windows)
   hfp::Jac<HF> combine_windows(const void *host, int c) const;
-  std::vector<hfp::Jac<HF>> read_windows(hipStream_t s);            // set 0, waits
+  // One MSM at a time on set 0, coop, ending in bit sums when the plan has them
+  void launch(hipStream_t s, const void *S) {
+    ensure(0, 1);
+    head(s, S, size(), 0, 0, 1);
+    tail(s, 0, 1, sync_ending(), true);
+  }
+  std::vector<hfp::Jac<HF>> read_windows(hipStream_t s);  // waits
   hfp::Jac<HF> read(hipStream_t s) { return read_windows(s)[0]; }
-  // set 0's sum_w 2^(c w) T_w (after launch_tail), waits
-  hfp::Jac<HF> read_total(hipStream_t s, int c);
-  size_t size() const { return bsize_; }
+  hfp::Jac<HF> read_total(hipStream_t s, int c);  // sum_w 2^(c w) T_w, waits
+  size_t size() const { return plan_.nbuckets; }
   // device bytes held: plan tables, every buffer set (partials, dense slots and
-  // their ScanReducer buffers), the bit-phase read-back (engine pool budget)
+  // their ScanReducer buffers, finalized bit sums) (engine pool budget)
   size_t device_bytes() const {
-    size_t b = idx_.bytes + bfin_.bytes;
-    for (int t = 0; t < NSETS; ++t) b += bgfin_[t].bytes;
+    size_t b = idx_.bytes;
     for (const DevBuf &d : starts_) b += d.bytes;
-    for (const DevBuf &d : bstarts_) b += d.bytes;
     for (int t = 0; t < NSETS; ++t)
-      b += dense_buf_[t].bytes + part_[t][0].bytes + part_[t][1].bytes + dense_[t].buf[0].bytes +
+      b += dense_buf_[t].bytes + part_[t][0].bytes + part_[t][1].bytes + bgfin_[t].bytes + dense_[t].buf[0].bytes +
            dense_[t].buf[1].bytes + dense_[t].fin.bytes;
     return b;
   }
 
-  void ensure_set(int set);  // allocate buffer set `set` for the current plan
-
-  // Batch groups (Ches::run_batch): the reduction plan is the same for every
-  // MSM, so nmsm MSMs share buffer set `set` -- each MSM's level 0 writes its
-  // own slot, then ONE launch per tail level reduces all slots together.  A
-  // batch then issues ~35 tail launches per group instead of per MSM (every
-  // launch beside an accumulation costs it time).
-  void ensure_group(int set, int nmsm);
-  void launch_head_slot(hipStream_t s, const void *S, int set, int slot);
-  // level 0 of nmsm consecutive MSMs (slots slot0 .. slot0 + nmsm - 1 of set
-  // `set`) in one launch; MSM j's buckets at S + j sstride points
-  void launch_head_slots(hipStream_t s, const void *S, size_t sstride, int set, int slot0, int nmsm);
-  // the operands of level 0 into slot `slot` of set `set` (k_segsum)
-  struct HeadArgs {
-    const uint32_t *idx, *starts;
-    void *dst;
-    size_t nout;
-  };
-  HeadArgs head_args(int set, int slot);
-  // levels >= 1, dense, finalize; coop: the dense stage's adds over 4 waves each
-  // (shortest latency when nothing else runs, e.g. the last group of a batch)
-  void launch_tail_group(hipStream_t s, int set, int nmsm, bool coop = false);
-  void copy_out_group(hipStream_t s, int set, int nmsm, void *host);  // nmsm * out_bytes()
-  // the same group tail ending in 2 s bit sums per MSM instead of the dense
-  // stage (one-window plans with a segment phase: has_bit_tail()); the host
-  // gets nmsm * bit_bytes() and combine_bits(MSM j's bytes) = combine(...)[0]
-  bool has_bit_tail() const { return bits_ && nout_.size() >= 2; }
-  size_t bit_bytes() const { return bit_slots() * 144 * G; }
-  void launch_tail_group_bits(hipStream_t s, int set, int nmsm, bool coop = false);
-  void copy_out_group_bits(hipStream_t s, int set, int nmsm, void *host);
-  hfp::Jac<HF> combine_bits(const void *host) const;
-
  private:
-  size_t dense_slots() const { return (size_t)2 * nwin_ << sbits_; }
-  size_t bit_slots() const { return (size_t)2 * nwin_ * sbits_; }
-  size_t bsize_ = 0, final_perm_off_ = 0, maxp_ = 1;
-  size_t maxp1_ = 1;  // batch groups: partials per MSM in part_[.][1] (the odd tail levels)
-  int sbits_ = 1, nwin_ = 1, c0_ = 8;
+  ReduceEnding sync_ending() const { return has_bit_tail() ? kEndBits : kEndDense; }
+  const DevBuf &buf(int set, ReduceBuf b) const { return b == kRedDense ? dense_buf_[set] : part_[set][b == kRedPart1]; }
+  ReducePlan plan_;
+  std::vector<ReduceStep> steps_[2];  // by ending (kEndBits: empty without a bit tail)
   DevBuf idx_, dense_buf_[NSETS], part_[NSETS][2];
-  std::vector<DevBuf> starts_;
-  std::vector<size_t> nout_;
+  std::vector<DevBuf> starts_;  // by ReduceStep::level
   ScanReducer<G> dense_[NSETS];
-  // Synchronous tail of a one-window plan (launch_tail / read_windows): the
-  // dense 2 x 2^s stage (2 s dependent levels) is replaced by 2 s bit sums
-  // B_j = sum of the partials whose value has bit j (j < s: low half, j >= s:
-  // high half), ~log2(2^s s / 8) + 2 levels, and a 2 s-step host Horner
-  // (T = sum_j 2^j B_j).  Batch groups keep the dense stage (one per group).
-  bool bits_ = false;
-  size_t bidx_off_ = 0, bperm_off_ = 0;
-  std::vector<DevBuf> bstarts_;
-  std::vector<size_t> bnout_;
-  DevBuf bfin_;
-  DevBuf bgfin_[NSETS];  // group bit tails: nmsm x 2 s finalized bit sums per set
+  DevBuf bgfin_[NSETS];  // bit endings: nmsm x 2 s finalized bit sums per set
 };
 
 // digit/sort outputs of one MSM (entries sorted by bucket + schedule); the
@@ -466,7 +428,7 @@ class Ches {
   hipEvent_t ev_tail_[kBSets] = {nullptr, nullptr};
   void *host_out_ = nullptr;
   size_t host_out_bytes_ = 0;
-  void *host_bits_ = nullptr;  // the last group's bit-tail read-back (WeightedReducer::launch_tail_group_bits)
+  void *host_bits_ = nullptr;  // the last group's bit-tail read-back (WeightedReducer::tail, kEndBits)
   size_t host_bits_bytes_ = 0;
   std::vector<hipEvent_t> bev_;     // batch dependency events, one per (MSM, stage)
   std::vector<hipEvent_t> acc_ev_;  // batch profiling: events around each accumulation

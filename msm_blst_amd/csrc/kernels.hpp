@@ -9,8 +9,8 @@
 //                 bucket schedule = ids sorted by count, descending, so a
 //                 wavefront's 64 buckets are equally long
 //   k_accumulate  one lane per bucket: xyzz += +-P over its sorted points
-//   reduction     WeightedReducer (ches.hip): segment sums by weight bits,
-//                 dense suffix-scan stage (sum_b b*B_b)
+//   reduction     WeightedReducer (plan: reduce_plan.hpp, launches: ches.hip):
+//                 segment sums by weight bits, dense suffix-scan stage (sum_b b*B_b)
 //   k_finalize    window totals -> blst Jacobian (R=2^384 Montgomery)
 // CHES pipeline: see ches.hpp.
 #pragma once

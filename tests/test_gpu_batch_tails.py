@@ -1,7 +1,7 @@
 """GPU parity of round 6's batch tails (ches.hip / engine.hip).
 
 The batch's LAST reduction group of a one-window CHES plan ends in 2 s bit sums
-per MSM and a host Horner (WeightedReducer::launch_tail_group_bits) instead of
+per MSM and a host Horner (WeightedReducer::tail ending in kEndBits) instead of
 the dense stage; earlier groups keep the dense stage, whose levels now run over
 4 waves per add only when they have <= 16 384 adds (MSM_DENSE_COOP_MAX).  The
 reduction they restate is ref src/multi_scalar.c:301-321 (sum_b b S_b over the

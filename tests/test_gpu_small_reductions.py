@@ -1,8 +1,8 @@
 """GPU parity of the one-window reductions at tiny sizes (CHES and BGMW95,
 G1 and G2): with a handful of points the final segment partials are few and
-sparse, which is where the synchronous bit-sum tail (WeightedReducer plan:
-2 s bit sums + host Horner, ches.hip) has its smallest buffers and emptiest
-bit segments.  Checked against the oracle's naive MSM (oracle/msm_oracle.c),
+sparse, which is where the synchronous bit-sum tail (ReducePlan's bit phase,
+reduce_plan.hpp: 2 s bit sums + host Horner) has its smallest buffers and
+emptiest bit segments.  Checked against the oracle's naive MSM (oracle/msm_oracle.c),
 the reference's result on the same inputs (ref main_p1.cpp:470-580 compares
 every method with Pippenger)."""
 import ctypes

@@ -8,8 +8,13 @@ knob setting is the environment of one run of this script.  Run under
 tools/hip_trace_compare.py compares between two builds; the GPU test
 tests/test_gpu_batch_schedules.py runs it plain.
 
-usage: batch_cases.py <repo> ches|plain|segments|profile [K] [device|pinned|pageable ...]
+Kind `sync` is no batch: one synchronous mult each of CHES G1 2^12 and G2 2^10,
+BGMW95 G1, the plain engine G1 and blst_p1s_mult_pippenger through the drop-in,
+each against the plain engine's result.
+
+usage: batch_cases.py <repo> ches|plain|segments|profile|sync [K] [device|pinned|pageable ...]
 prints one line per call and OK or MISMATCH last; exit status 1 on a mismatch."""
+import ctypes
 import sys
 
 sys.path.insert(0, sys.argv[1])
@@ -42,8 +47,45 @@ def batch_twice(ctx, group, raw, src, on_device, K, n, **kw):
     return ok
 
 
+def sync_cases():
+    """one synchronous MSM per engine; every result equal to the plain engine's"""
+    ok = True
+    for group, lg in SHAPES:
+        n = 1 << lg
+        pts, sc = m.fixed_points(group, n), m.gen_scalars(n, 1)
+        ref = m.MSMContext(group, 0, 10)
+        ref.set_points(pts, n)
+        want = m.compress(group, ref.mult(sc, nbits=255))
+        ref.close()
+        got = {}
+        ches = m.CHESContext(group, 0, n_exp=lg)
+        ches.build_table(pts, n)
+        got["ches"] = m.compress(group, ches.mult(sc))
+        ches.close()
+        if group == 1:
+            bgmw = m.BGMWContext(group, 0, n_exp=lg)
+            bgmw.build_table(pts, n)
+            got["bgmw"] = m.compress(group, bgmw.mult(sc))
+            bgmw.close()
+            S = (ctypes.c_uint8 * len(sc)).from_buffer_copy(bytes(sc))
+            pp = (ctypes.c_void_p * 2)(ctypes.cast(pts, ctypes.c_void_p), None)
+            sp = (ctypes.c_void_p * 2)(ctypes.cast(S, ctypes.c_void_p), None)
+            r = (ctypes.c_uint8 * 144)()
+            m.lib().blst_p1s_mult_pippenger(r, pp, n, sp, 255, None)
+            got["dropin"] = m.compress(group, r)
+        for name, g in got.items():
+            print(f"CALL sync {name} G{group} n=2^{lg} {'ok' if g == want else 'MISMATCH'}", flush=True)
+            ok &= g == want
+    return ok
+
+
 def main():
     kind = sys.argv[2]
+    if kind == "sync":
+        torch.cuda.init()
+        ok = sync_cases()
+        print("OK" if ok else "MISMATCH")
+        return 0 if ok else 1
     K = int(sys.argv[3]) if len(sys.argv) > 3 else 19
     wheres = sys.argv[4:] or ["device", "pinned"]
     ok = True

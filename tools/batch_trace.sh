@@ -41,3 +41,5 @@ t plain "" plain 19 device pinned
 t plain_group2 "MSM_PIP_GROUP=2" plain 19 device pinned
 t plain_fg1 "MSM_PIP_FRONT_GROUP=1" plain 19 device pinned
 t plain_fg8 "MSM_PIP_FRONT_GROUP=8" plain 19 device pinned
+# no batch: one synchronous MSM per engine (compare with --no-alloc: the reducer's buffer sizing)
+t sync "" sync

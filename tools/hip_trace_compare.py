@@ -9,7 +9,8 @@ direction and byte count of a copy or memset, and the kernel (by name where the
 trace maps its host function, else numbered by first appearance) with grid and
 block of a launch.  Addresses of buffers, and everything else, are left out.
 
-usage: hip_trace_compare.py <a_results.json> <b_results.json> [--show N]
+usage: hip_trace_compare.py <a_results.json> <b_results.json> [--show N] [--no-alloc]
+       --no-alloc leaves hipMalloc / hipFree out (two builds that size or allocate their buffers differently)
        hip_trace_compare.py --reduce <results.json> <out.json.gz>   (a smaller file the first form also reads)
 prints EQUAL and the call count, or the first N differing calls; exit status 1
 if the traces differ."""
@@ -46,7 +47,10 @@ def load(path):
     return list(threads.values()), kernels
 
 
-def reduce_calls(calls, kernels):
+ALLOC = ("hipMalloc", "hipFree")
+
+
+def reduce_calls(calls, kernels, no_alloc=False):
     seen = {"s": {}, "e": {}, "k": {}}
     count = {"s": 0, "e": 0, "k": 0}
 
@@ -58,6 +62,8 @@ def reduce_calls(calls, kernels):
 
     out = []
     for name, args in calls:
+        if no_alloc and name in ALLOC:
+            continue
         item = [name]
         for a in args:
             n, v = a["name"], a.get("value")
@@ -86,13 +92,14 @@ def main():
             json.dump({"reduced": threads, "kernels": kernels}, f)
         return 0
     show = int(sys.argv[sys.argv.index("--show") + 1]) if "--show" in sys.argv else 5
+    no_alloc = "--no-alloc" in sys.argv
     (ta, ka), (tb, kb) = load(sys.argv[1]), load(sys.argv[2])
     if len(ta) != len(tb):
         print(f"DIFFER threads that call HIP: {len(ta)} vs {len(tb)}")
         return 1
     total = diffs = 0
     for i, (ca, cb) in enumerate(zip(ta, tb)):
-        ra, rb = reduce_calls(ca, ka), reduce_calls(cb, kb)
+        ra, rb = reduce_calls(ca, ka, no_alloc), reduce_calls(cb, kb, no_alloc)
         total += len(ra)
         if len(ra) != len(rb):
             print(f"DIFFER thread {i}: {len(ra)} vs {len(rb)} calls")
