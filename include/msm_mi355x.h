@@ -952,6 +952,47 @@ int msm_test_xyzz(int group, const void *points_affine, size_t npoints, const ui
  * result's.  b is read by ops 0 and 2 only.  n == 0: MSM_OK.  MSM_E_ARG, before any
  * device work: an unknown op, alias or raw, k out of range, a NULL array that is used. */
 int msm_test_fp12(int op, int k, int alias, int raw, const void *a, const void *b, void *out, size_t n);
+/* one operation of the field and curve layers under every product kernel (csrc/fp.hpp,
+ * fp2l.hpp, ec.hpp, coop.hpp) on n values, on device 0, synchronously, on raw stored
+ * words: an element is 14 little-endian 28-bit limbs in uint32 (Fp) or two of them, c0 |
+ * c1 (Fp2, Fp2L), of value 2^392 mod p, in and out untouched, so the caller chooses the
+ * representative (any limbs the op's range class allows, lazy ones included) and sees
+ * the result's.
+ * field: 0 Fp, one lane per value; 1 Fp2, one lane per value; 2 Fp2L, value i on lanes 2i
+ *   (c0) and 2i + 1 (c1) of 64-thread blocks, 32 values per block.
+ * form: 0 split Montgomery columns, 1 the single chain (MulChain; Fp only, ops marked *).
+ * op, with the elements it reads per value (in = n x that many, value after value):
+ *    0 f_mul* (a, b)          1 f_mul_bs* (a, b)        2 f_sqr* (a)
+ *    3 f_mul_sub* (a, b, c, d) = a b - c d              4 f_mul_sub_bs* (a, b, c, d)
+ *    5 f_add (a, b)           6 f_sub4 (a, b)           7 f_sub16 (a, b)
+ *    8 fp_sub<8> (a, b)       9 fp_sub<32> (a, b), both per component
+ *   10 f_sub_2x (a, b, c) = a + 8p - b - 2c            11 f_neg4 (a)    12 f_mul3 (a)
+ *   13 f_norm (a)            14 f_nred (a)             15 f_one ()
+ *   16 f_is_zero_exact (a)   17 f_is_zero_S (a): out is one uint32 per value, 0 or 1
+ *      (Fp2L: the even lane's verdict, which is the pair's)
+ *   Fp only: 18 fp_mul2* (a, b, c, d) = a b + c d      19 fp_mul4* (a .. h) = a b + c d +
+ *      e f + g h             20 fp_red (a)             21 fp_cneg4 (a; flag bit 0)
+ *      22 fp_canon (a)       23 fp_csub_p (a)
+ *   curve ops, points as stored (x, y, zzz, zz), out = the xyzz result:
+ *   24 xyzz_madd* (acc, then the affine x2, y2; flags bit 0: neg, bit 1: acc_affine -- the
+ *      accumulator is then xyzz_from_aff of (acc.x, acc.y) with sign bit 2, zzz and zz
+ *      unread; the flags of a value hold for both lanes of an Fp2L pair)
+ *   25 xyzz_add* (acc, b), the field's default instantiation   26 xyzz_add_u1s1* (acc, b)
+ *   27 xyzz_dbl* (a)
+ *   28 the cooperative add of coop.hpp through the reductions' own kernels: field 0
+ *      k_pair_step_c<1>, field 2 k_pair_step_c2p, out[i] = in[2i] + in[2i + 1] (field 1
+ *      has no such kernel: MSM_E_ARG)
+ *   Every combination above is built, none was left out for its registers, except op 4
+ *   on field 1: fp.hpp has no f_mul_sub_bs over the one-lane Fp2 (MSM_E_ARG).
+ * flags: one uint32 per value, read by ops 21 and 24 only.  out: cap >= n slots (an
+ * element, a point or a word each); all cap slots go to the device as the caller filled
+ * them and come back, so a slot from n on returns as it went in unless a kernel wrote
+ * past its n.  n == 0: MSM_OK.  MSM_E_ARG, before any device work: an unknown field, form
+ * or op, form 1 for an op or field without it, an Fp-only op on another field, cap < n,
+ * a NULL array that is used (in unless the op reads nothing, flags for ops 21 and 24,
+ * out). */
+int msm_test_fp_ops(int field, int form, int op, const uint32_t *in, const uint32_t *flags, uint32_t *out, size_t n,
+                    size_t cap);
 
 #ifdef __cplusplus
 }

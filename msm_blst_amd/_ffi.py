@@ -54,6 +54,7 @@ def lib():
     L.msm_test_field.argtypes = [i32, i32, vp, vp, vp, sz]
     L.msm_test_xyzz.argtypes = [i32, vp, sz, vp, i32, sz, vp]
     L.msm_test_fp12.argtypes = [i32, i32, i32, i32, vp, vp, vp, sz]
+    L.msm_test_fp_ops.argtypes = [i32, i32, i32, vp, vp, vp, sz, sz]
     pp = ctypes.POINTER(vp)
     L.msm_ches_params.argtypes = [i32, i32, vp]
     L.msm_ches_ctx_create.argtypes = [pp, i32, i32, i32, i32]

@@ -33,7 +33,7 @@ SOURCES = [("engine.hip", 1), ("engine.hip", 2), ("ches.hip", 1), ("ches.hip", 2
            ("points_mult.hip", 1), ("points_mult.hip", 2), ("encode.hip", 1), ("encode.hip", 2),
            ("point_segments.hip", 1), ("point_segments.hip", 2),
            ("hash_to_curve.hip", 1), ("hash_to_curve.hip", 2),
-           ("pairing.hip", None), ("sig_verify.hip", None), ("fr_ntt.hip", None), ("fr_poly.hip", None), ("kzg.cpp", None), ("probe.hip", None), ("abi.cpp", None)]
+           ("pairing.hip", None), ("sig_verify.hip", None), ("fr_ntt.hip", None), ("fr_poly.hip", None), ("kzg.cpp", None), ("probe.hip", None), ("fp_ops_test.hip", None), ("abi.cpp", None)]
 
 
 def _deps():

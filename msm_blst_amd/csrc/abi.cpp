@@ -24,6 +24,7 @@
 #include "encode.hpp"
 #include "engine.hpp"
 #include "fr_ntt.hpp"
+#include "fp_ops_test.hpp"
 #include "fr_poly.hpp"
 #include "hash_to_curve.hpp"
 #include "host_fr.hpp"
@@ -2086,6 +2087,28 @@ int msm_test_fp12(int op, int k, int alias, int raw, const void *a, const void *
   if (!device_ok(0)) return no_device();
   return guarded(MSM_E_HIP, [&] {
     test_fp12(op, k, alias, raw != 0, a, binary ? b : nullptr, out, n);
+    return MSM_OK;
+  });
+}
+int msm_test_fp_ops(int field, int form, int op, const uint32_t *in, const uint32_t *flags, uint32_t *out, size_t n,
+                    size_t cap) {
+  const TestFpOp *d = test_fp_op(op);
+  if (!d) return fail(MSM_E_ARG, "unknown op");
+  if (field < TEST_FIELD_FP || field > TEST_FIELD_FP2L) return fail(MSM_E_ARG, "unknown field");
+  if (form != TEST_FORM_SPLIT && form != TEST_FORM_CHAIN) return fail(MSM_E_ARG, "unknown form");
+  if (form == TEST_FORM_CHAIN && (!d->forms || field != TEST_FIELD_FP))
+    return fail(MSM_E_ARG, "no single-chain form of this op on this field");
+  if (d->fp_only && field != TEST_FIELD_FP) return fail(MSM_E_ARG, "an Fp-only op");
+  if ((op == TEST_COOP_ADD || op == TEST_F_MUL_SUB_BS) && field == TEST_FIELD_FP2)
+    return fail(MSM_E_ARG, "the one-lane Fp2 has no f_mul_sub_bs and no cooperative kernel");
+  if (cap < n) return fail(MSM_E_ARG, "cap < n");
+  if (n && ((d->nin && !in) || (d->flags && !flags) || !out)) return fail(MSM_E_ARG, "null operand");
+  if (!n) return MSM_OK;
+  if (!device_ok(0)) return no_device();
+  return guarded(MSM_E_HIP, [&] {
+    if (op != TEST_COOP_ADD) test_fp_ops(field, form, op, in, flags, out, n, cap);
+    else if (field == TEST_FIELD_FP) test_coop_pair_add<1>(in, out, n, cap);
+    else test_coop_pair_add<2>(in, out, n, cap);
     return MSM_OK;
   });
 }

@@ -24,6 +24,7 @@
 #include "ches_kernels.hpp"
 #include "coop.hpp"
 #include "engine.hpp"
+#include "fp_ops_test.hpp"
 #include "hoststage.hpp"
 #include "pair_kernels.hpp"
 
@@ -812,5 +813,30 @@ void Ches<G>::run_jobs(hipStream_t s, const uint8_t *scalars, size_t stride, siz
 }
 
 template class Ches<MSM_GROUP>;
+
+// msm_test_fp_ops, op 28 (fp_ops_test.hpp): the cooperative add through the
+// dense stage's own pair step, launched as launch_pair_step launches it, on
+// device 0, synchronously.  The whole out buffer makes the round trip, so the
+// caller sees whether a slot past n was written.
+template <int G>
+void test_coop_pair_add(const uint32_t *in, uint32_t *out, size_t n, size_t cap) {
+  typedef typename FieldOf<G>::F F;
+  if (!n) return;
+  DeviceGuard g(0);
+  DevBuf din, dout;
+  din.ensure(2 * n * sizeof(Xyzz<F>));
+  dout.ensure(cap * sizeof(Xyzz<F>));
+  MSM_HIP_CHECK(hipMemcpy(din.p, in, 2 * n * sizeof(Xyzz<F>), hipMemcpyHostToDevice));
+  MSM_HIP_CHECK(hipMemcpy(dout.p, out, cap * sizeof(Xyzz<F>), hipMemcpyHostToDevice));
+  // (not through launch_pair_step: MSM_DENSE_COOP_MAX must not choose another kernel here)
+  if constexpr (G == 2)
+    hipLaunchKernelGGL(k_pair_step_c2p, dim3(nblk(n, 32)), dim3(256), 0, 0, din.as<Xyzz<F>>(), dout.as<Xyzz<F>>(), n);
+  else
+    hipLaunchKernelGGL(k_pair_step_c<G>, dim3(nblk(n, 64)), dim3(256), 0, 0, din.as<Xyzz<F>>(), dout.as<Xyzz<F>>(), n);
+  MSM_HIP_CHECK(hipGetLastError());
+  MSM_HIP_CHECK(hipDeviceSynchronize());
+  MSM_HIP_CHECK(hipMemcpy(out, dout.p, cap * sizeof(Xyzz<F>), hipMemcpyDeviceToHost));
+}
+template void test_coop_pair_add<MSM_GROUP>(const uint32_t *, uint32_t *, size_t, size_t);
 
 }  // namespace msm

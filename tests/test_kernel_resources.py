@@ -45,7 +45,8 @@ def test_every_kernel_found(kernels):
     names = " ".join(kernels)
     for k in ("k_accumulate", "k_accumulate2p", "k_segsum", "k_segsum2p", "k_ches_table", "k_ches_table2p",
               "k_ches_front_hist", "k_finalize", "k_wbits_table2p", "k_wbits_sums2p", "k_test_xyzz2p",
-              "k_test_fp12", "k_test_fp12_inv", "k_test_fp12_line"):
+              "k_test_fp12", "k_test_fp12_inv", "k_test_fp12_line", "k_fpt_field", "k_fpt_zero", "k_fpt_fp",
+              "k_fpt_curve"):
         assert k in names, k
 
 
