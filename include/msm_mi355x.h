@@ -893,8 +893,14 @@ int msm_fr_probe(int device, double out[2]);
  * than (nbits + 7) / 8, a decreasing batch offset or one past count.  MSM_E_NODEV: no
  * such device.  MSM_E_HIP: a HIP failure; host outputs are then zero-filled, ok filled
  * with 0 and *nfail set to the number of verdicts.
- * Out of scope: turning a monomial SRS into the Lagrange one, EIP-4844's Fiat-Shamir
- * challenge and big-endian field bytes, multi-point openings, G2 commitments. */
+ * msm_kzg_ctx_create_monomial: the same context from an SRS in MONOMIAL form, as a
+ * trusted setup publishes it: srs_monomial_g1 holds the n points [tau^i]G1, i in natural
+ * order, host or device memory.  The context is the one msm_kzg_ctx_create builds from
+ * the inverse msm_points_ntt (below) of those points, bit-reversed when `flags` has
+ * MSM_POLY_BITREV; the transform runs on the device and its result never visits the
+ * host.  Guards and codes as msm_kzg_ctx_create; returns after the transform is done.
+ * Out of scope: EIP-4844's Fiat-Shamir challenge and big-endian field bytes,
+ * multi-point openings (FK20), G2 commitments. */
 enum { MSM_POLY_BITREV = 8 }; /* shares the flag word with MSM_FR_DST_SCALAR (4) */
 int msm_fr_eval_quotient(int device, void *y, void *q, const void *polys, const void *z, size_t log_n, size_t count,
                          int flags, int src_on_device, int dst_on_device, void *hip_stream);
@@ -910,6 +916,50 @@ int msm_kzg_verify(msm_kzg_ctx *ctx, uint8_t *ok, size_t *nfail, const void *com
                    const void *y, const void *proofs, size_t count, const byte *weights, size_t nbits,
                    size_t weight_stride, const size_t *batch_offsets, size_t nbatches, int src_on_device,
                    void *hip_stream);
+int msm_kzg_ctx_create_monomial(msm_kzg_ctx **ctx, int device, size_t log_n, const void *srs_monomial_g1,
+                                int srs_on_device, const void *tau_g2, int flags, void *hip_stream);
+
+/* ---- NTTs over group elements (the change of basis of an SRS or of committed data: the
+ * loop over blst_p{1,2}_mult and blst_p{1,2}_add_or_double a setup or an FK20 prover
+ * writes; no single reference counterpart) ----
+ * msm_points_ntt: `batch` transforms over consecutive arrays of n = 2^log_n affine points
+ * (blst_p1_affine / blst_p2_affine, group 1 / 2; the all-zero point is infinity, legal on
+ * input and on output), on the domain of msm_fr_ntt, omega_n = msm_fr_root_of_unity(log_n):
+ *   forward            dst[k] = sum_j [omega_n^(j k)] src[j]
+ *   MSM_NTT_INVERSE    dst[j] = [n^-1] sum_k [omega_n^(-j k)] src[k]
+ *   MSM_POLY_BITREV    the evaluation side is in bit-reversed order: the inverse writes
+ *                      result j at position bitrev(j, log_n), the forward transform reads
+ *                      its source element j at position bitrev(j, log_n); forward after
+ *                      inverse, both under the flag, is the identity, and the inverse of a
+ *                      monomial SRS is what msm_kzg_ctx_create(.., MSM_POLY_BITREV) wants
+ * log_n = 0 is a copy (through the canonical form).  dst may equal src.  log_n <= 24.
+ * The points MUST lie in the prime-order subgroup; they are not validated (chain
+ * msm_points_decode / msm_points_in_group first).  Outside the subgroup the result is
+ * unspecified: the factorisation of the twiddles into levels holds mod r only.  Within
+ * it every output is the canonical affine point, byte for byte.
+ * On the GPU: csrc/points_ntt.hip on the plan of csrc/points_ntt_plan.hpp (DESIGN section
+ * 31): radix-2 decimation in frequency on xyzz points; per level one general add and one
+ * subtraction per butterfly, then the 255-bit signed-window ladder of msm_points_mult
+ * on the difference with the twiddle as its scalar (the last level has none); the inverse
+ * adds one ladder per element for n^-1; one batch inversion at the end.  Chunks of whole
+ * transforms of at most 2^20 points (MSM_POINTS_NTT_CHUNK=<points> overrides; a longer
+ * transform is a chunk of its own); the butterflies of a chunk's level run in slices of
+ * at most 2^18 (MSM_POINTS_NTT_SLICE=<butterflies> overrides; both read at each call).
+ * Twiddle tables (16 n + 32 bytes) are kept per engine and log_n; engines are pooled per
+ * (device, group) and counted by msm_engine_cache_stats().  Host memory goes through the
+ * pinned staging of the other bulk calls; streams as msm_points_to_affine.
+ * batch == 0: MSM_OK, nothing touched.  MSM_E_ARG, before any device work: a NULL
+ * pointer with work to do, a group other than 1 or 2, log_n > 24 or batch n > 2^40,
+ * unknown flag bits, a dst that overlaps src without equalling it, misaligned device
+ * pointers.  MSM_E_NODEV: no such device.  MSM_E_HIP: a HIP failure; a host dst is then
+ * zero-filled.
+ * msm_points_ntt_model (host only, no device work): the same plan -- maps, levels with
+ * their pairs and exponents, the n^-1 pass, slices and chunks under the two overrides --
+ * run on blst_fr elements in place of points (the group Z_r), so the schedule can be
+ * checked on the CPU against any Fr NTT.  log_n <= 16, else MSM_E_ARG; dst may be src. */
+int msm_points_ntt(int group, int device, void *dst_affine, const void *src_affine, size_t log_n, size_t batch,
+                   int flags, int src_on_device, int dst_on_device, void *hip_stream);
+int msm_points_ntt_model(size_t log_n, int flags, blst_fr *dst, const blst_fr *src);
 
 /* host setup logic of the CHES method (no device work):
  * bucket set of ref auxiliaryfunc.h:257-288 (returns |B|; out may be NULL) */

@@ -36,7 +36,11 @@ Mirrors:
                                                       reference counterpart: the loop a KZG prover writes over blst_fr_*)
   KZGContext                                          commit / open / verify over a Lagrange-form SRS: the chain of
                                                       blst_p1s_mult_pippenger, blst_p1_mult and blst_miller_loop /
-                                                      blst_final_exp calls of a KZG prover and verifier, on the GPU
+                                                      blst_final_exp calls of a KZG prover and verifier, on the GPU;
+                                                      KZGContext.from_monomial builds it from powers of tau
+  ps_ntt, ntt_model                                   NTTs over G1 / G2 points (no reference counterpart: the loop over
+                                                      blst_p{1,2}_mult and blst_p{1,2}_add_or_double that changes the basis
+                                                      of an SRS), on the GPU, and the host model of their schedule
 """
 import ctypes
 
@@ -53,7 +57,7 @@ __all__ = ["MsmError", "MSMContext", "CHESContext", "BGMWContext", "WbitsContext
            "ps_verify", "ps_aggregate_verify", "ps_batch_verify", "ps_in_group", "sigs_plan", "sigs_reduce",
            "SIG_MIN_PK", "SIG_MIN_SIG",
            "fr_ntt", "fr_op", "fr_root_of_unity", "ntt_plan", "fr_probe", "FR_OPS",
-           "fr_eval_quotient", "KZGContext", "POLY_BITREV",
+           "fr_eval_quotient", "KZGContext", "POLY_BITREV", "ps_ntt", "ntt_model",
            "SRC_AFFINE", "SRC_JACOBIAN", "device_count", "lib"]
 
 POINT_BYTES = {1: 96, 2: 192}
@@ -392,6 +396,47 @@ def fr_eval_quotient(polys, z, log_n, count=1, *, want_q=True, dst_scalar=False,
     return bytes(y)[:count * FR_BYTES], (bytes(q)[:nbytes] if want_q else None)
 
 
+def ps_ntt(group, points, log_n, batch=1, *, inverse=False, bitrev=False, src_on_device=False, dst=None, device=0,
+           stream=None):
+    """`batch` transforms of 2^log_n affine points each through msm_points_ntt, on the
+    domain of fr_ntt: forward dst[k] = sum_j [omega_n^(j k)] src[j], inverse dst[j] =
+    [n^-1] sum_k [omega_n^(-j k)] src[k].  bitrev puts the evaluation side in bit-reversed
+    order (the inverse writes result j at bitrev(j), the forward transform reads element j
+    at bitrev(j)).  The points must lie in the prime-order subgroup (not validated); the
+    all-zero point is infinity.  A host source is a bytes-like object, a device source
+    (src_on_device) a device pointer.  Without dst the result comes back as bytes; with
+    dst=<device pointer> (which may be the source) it is written there, ordered on
+    `stream`, and None is returned."""
+    if group not in POINT_BYTES:
+        raise ValueError("group must be 1 or 2")
+    if not 0 <= log_n <= 24:
+        raise ValueError("log_n must be in [0, 24]")
+    if batch < 0:
+        raise ValueError("batch must be >= 0")
+    nbytes = (batch << log_n) * POINT_BYTES[group]
+    src = points if src_on_device else _fr_host(points, nbytes, "points")
+    flags = (NTT_INVERSE if inverse else 0) | (POLY_BITREV if bitrev else 0)
+    if dst is not None:
+        check(lib().msm_points_ntt(group, device, dst, src, log_n, batch, flags, int(bool(src_on_device)), 1, stream))
+        return None
+    out = (ctypes.c_uint8 * max(nbytes, 1))()
+    check(lib().msm_points_ntt(group, device, out, src, log_n, batch, flags, int(bool(src_on_device)), 0, stream))
+    return bytes(out)[:nbytes]
+
+
+def ntt_model(data, log_n, *, inverse=False, bitrev=False):
+    """One transform of 2^log_n blst_fr elements by the schedule of ps_ntt run on the host
+    with Fr elements in place of points (msm_points_ntt_model; log_n <= 16), under the
+    MSM_POINTS_NTT_SLICE / MSM_POINTS_NTT_CHUNK set now."""
+    if not 0 <= log_n <= 16:
+        raise ValueError("log_n must be in [0, 16]")
+    nbytes = FR_BYTES << log_n
+    src = _fr_host(data, nbytes, "elements")
+    out = (ctypes.c_uint8 * nbytes)()
+    check(lib().msm_points_ntt_model(log_n, (NTT_INVERSE if inverse else 0) | (POLY_BITREV if bitrev else 0), out, src))
+    return bytes(out)
+
+
 class KZGContext:
     """KZG over one Lagrange-form SRS (msm_kzg_*): srs is 2^log_n blst_p1_affine points
     L_i = [l_i(tau)]G1 in the order of the polynomials (natural, or bit-reversed with
@@ -408,6 +453,24 @@ class KZGContext:
         self._h = ctypes.c_void_p()
         check(lib().msm_kzg_ctx_create(ctypes.byref(self._h), device, log_n, src, int(bool(srs_on_device)), tau,
                                        POLY_BITREV if bitrev else 0, stream))
+
+    @classmethod
+    def from_monomial(cls, log_n, srs_monomial, tau_g2, *, bitrev=False, srs_on_device=False, device=0, stream=None):
+        """The context over the SRS given in monomial form: 2^log_n blst_p1_affine points
+        [tau^i]G1, i in natural order (msm_kzg_ctx_create_monomial: their inverse ps_ntt on
+        the device, bit-reversed with bitrev)."""
+        if not 0 <= log_n <= 20:
+            raise ValueError("log_n must be in [0, 20]")
+        self = cls.__new__(cls)
+        self._h = None
+        self.log_n, self.n, self.device, self.bitrev = log_n, 1 << log_n, device, bool(bitrev)
+        src = srs_monomial if srs_on_device else _fr_host(srs_monomial, self.n * POINT_BYTES[1], "SRS points")
+        tau = _fr_host(tau_g2, POINT_BYTES[2], "tau_g2")
+        h = ctypes.c_void_p()
+        check(lib().msm_kzg_ctx_create_monomial(ctypes.byref(h), device, log_n, src, int(bool(srs_on_device)), tau,
+                                                POLY_BITREV if bitrev else 0, stream))
+        self._h = h
+        return self
 
     def commit(self, polys, count=1, *, src_on_device=False, dst=None, stream=None):
         """count commitments [f_j(tau)]G1 (bytes; with dst=<device pointer> written there, None returned)"""

@@ -166,6 +166,9 @@ def lib():
     L.msm_kzg_commit.argtypes = [vp, vp, vp, sz, i32, i32, vp]
     L.msm_kzg_open.argtypes = [vp, vp, vp, vp, vp, sz, i32, i32, vp]
     L.msm_kzg_verify.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, vp, sz, i32, vp]
+    L.msm_kzg_ctx_create_monomial.argtypes = [pp, i32, sz, vp, i32, vp, i32, vp]
+    L.msm_points_ntt.argtypes = [i32, i32, vp, vp, sz, sz, i32, i32, i32, vp]
+    L.msm_points_ntt_model.argtypes = [sz, i32, vp, vp]
     _lib = L
     return L
 

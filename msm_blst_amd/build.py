@@ -30,7 +30,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 SOURCES = [("engine.hip", 1), ("engine.hip", 2), ("ches.hip", 1), ("ches.hip", 2), ("bgmw.hip", 1), ("bgmw.hip", 2),
            ("compat.hip", 1), ("compat.hip", 2), ("wbits.hip", 1), ("wbits.hip", 2),
            ("to_affine.hip", 1), ("to_affine.hip", 2), ("decode.hip", 1), ("decode.hip", 2),
-           ("points_mult.hip", 1), ("points_mult.hip", 2), ("encode.hip", 1), ("encode.hip", 2),
+           ("points_mult.hip", 1), ("points_mult.hip", 2), ("points_ntt.hip", 1), ("points_ntt.hip", 2), ("encode.hip", 1), ("encode.hip", 2),
            ("point_segments.hip", 1), ("point_segments.hip", 2),
            ("hash_to_curve.hip", 1), ("hash_to_curve.hip", 2),
            ("pairing.hip", None), ("sig_verify.hip", None), ("fr_ntt.hip", None), ("fr_poly.hip", None), ("kzg.cpp", None), ("probe.hip", None), ("fp_ops_test.hip", None), ("abi.cpp", None)]

@@ -33,6 +33,8 @@
 #include "pairing.hpp"
 #include "point_segments.hpp"
 #include "points_mult.hpp"
+#include "points_ntt.hpp"
+#include "points_ntt_model.hpp"
 #include "pool.hpp"
 #include "ptr_walk.hpp"
 #include "sig_verify.hpp"
@@ -531,6 +533,33 @@ int points_mult_checked(int group, int dev, void *dst, const void *points, const
   return guarded(MSM_E_HIP, [&] {
     by_group(group, [&](auto g) {
       points_mult<decltype(g)::value>(dev, dst, points, scalars, n, (int)nbits, stride, one, src_dev, dst_dev, user);
+    });
+    return MSM_OK;
+  }, on_throw);
+}
+
+// ---- NTTs over group elements (csrc/points_ntt.hip) ----
+int points_ntt_checked(int group, int dev, void *dst, const void *src, size_t log_n, size_t batch, int flags,
+                       bool src_dev, bool dst_dev, hipStream_t user) {
+  if (group != 1 && group != 2) return fail(MSM_E_ARG, "group must be 1 or 2");
+  if (log_n > (size_t)PN_MAX_LOG) return fail(MSM_E_ARG, "log_n above 24");
+  if (flags & ~(MSM_NTT_INVERSE | MSM_POLY_BITREV)) return fail(MSM_E_ARG, "unknown flag bits");
+  if (batch == 0) return MSM_OK;  // nothing touched
+  if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
+  if (batch > (((size_t)1 << 40) >> log_n)) return fail(MSM_E_ARG, "batch out of range");
+  const size_t bytes = (batch << log_n) * 96 * group;
+  if (src_dev == dst_dev && dst != src && ranges_overlap(src, bytes, dst, bytes))
+    return fail(MSM_E_ARG, "source and destination overlap");
+  if (src_dev && ((uintptr_t)src & 7) != 0) return fail(MSM_E_ARG, "device source not 8-byte aligned");
+  if (dst_dev && ((uintptr_t)dst & 7) != 0) return fail(MSM_E_ARG, "device destination not 8-byte aligned");
+  if (!device_ok(dev)) return no_device();
+  const auto on_throw = [&] { zero_host(dst, bytes, dst_dev); };
+  return guarded(MSM_E_HIP, [&] {
+    by_group(group, [&](auto g) {
+      constexpr int G = decltype(g)::value;
+      bulk_run<PointsNtt<G>>(dev, G, src_dev, dst_dev, user, [&](PointsNtt<G> &e, hipStream_t cs) {
+        e.run(cs, src, dst, (int)log_n, batch, flags, src_dev, dst_dev);
+      });
     });
     return MSM_OK;
   }, on_throw);
@@ -1342,6 +1371,24 @@ int msm_points_mult(int group, int device, void *dst, const void *points, const 
                              src_on_device != 0, dst_on_device != 0, (hipStream_t)hip_stream);
 }
 
+int msm_points_ntt(int group, int device, void *dst_affine, const void *src_affine, size_t log_n, size_t batch,
+                   int flags, int src_on_device, int dst_on_device, void *hip_stream) {
+  return points_ntt_checked(group, device, dst_affine, src_affine, log_n, batch, flags, src_on_device != 0,
+                            dst_on_device != 0, (hipStream_t)hip_stream);
+}
+
+int msm_points_ntt_model(size_t log_n, int flags, blst_fr *dst, const blst_fr *src) {
+  if (log_n > 16) return fail(MSM_E_ARG, "log_n above 16");
+  if (flags & ~(MSM_NTT_INVERSE | MSM_POLY_BITREV)) return fail(MSM_E_ARG, "unknown flag bits");
+  if (!dst || !src) return fail(MSM_E_ARG, "null dst / src");
+  static_assert(sizeof(blst_fr) == sizeof(hfr::Fr), "blst_fr");
+  return guarded(MSM_E_ARG, [&] {
+    pn_model((int)log_n, flags, 1, reinterpret_cast<hfr::Fr *>(dst), reinterpret_cast<const hfr::Fr *>(src), pn_chunk(),
+             pn_slice());
+    return MSM_OK;
+  });
+}
+
 int msm_points_encode(int group, int device, void *dst, const void *src, size_t npoints, int src_form, int encoding,
                       int flags, int src_on_device, int dst_on_device, void *hip_stream) {
   return points_encode_checked(group, device, dst, src, npoints, src_form, encoding, flags, src_on_device != 0,
@@ -1671,6 +1718,31 @@ int msm_kzg_ctx_create(msm_kzg_ctx **ctx, int device, size_t log_n, const void *
 }
 
 void msm_kzg_ctx_destroy(msm_kzg_ctx *ctx) { delete ctx; }
+
+int msm_kzg_ctx_create_monomial(msm_kzg_ctx **ctx, int device, size_t log_n, const void *srs_monomial_g1,
+                                int srs_on_device, const void *tau_g2, int flags, void *hip_stream) {
+  if (!ctx || !srs_monomial_g1 || !tau_g2) return fail(MSM_E_ARG, "null ctx / srs / tau_g2");
+  if (log_n > (size_t)KZG_MAX_LOG) return fail(MSM_E_ARG, "log_n above 20");
+  if (flags & ~MSM_POLY_BITREV) return fail(MSM_E_ARG, "unknown flag bits");
+  if (srs_on_device && ((uintptr_t)srs_monomial_g1 & 7) != 0) return fail(MSM_E_ARG, "device srs not 8-byte aligned");
+  if (!device_ok(device)) return no_device();
+  int rc = MSM_OK;
+  const int thrown = guarded(MSM_E_HIP, [&] {
+    // the Lagrange SRS: the inverse transform of the monomial one, device to device on the caller's stream
+    DeviceGuard g(device);
+    DevBuf lag;
+    lag.ensure(((size_t)96) << log_n);
+    rc = points_ntt_checked(1, device, lag.p, srs_monomial_g1, log_n, 1, MSM_NTT_INVERSE | (flags & MSM_POLY_BITREV),
+                            srs_on_device != 0, true, (hipStream_t)hip_stream);
+    if (rc != MSM_OK) return MSM_OK;
+    auto c = std::make_unique<msm_kzg_ctx>(device, (int)log_n, flags, auto_window((size_t)1 << log_n));
+    rc = c->k.set_srs(lag.p, true, tau_g2, (hipStream_t)hip_stream);
+    MSM_HIP_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));  // `lag` is freed here
+    if (rc == MSM_OK) *ctx = c.release();
+    return MSM_OK;
+  });
+  return thrown != MSM_OK ? thrown : rc;
+}
 
 int msm_kzg_commit(msm_kzg_ctx *ctx, void *dst_affine, const void *polys, size_t count, int src_on_device,
                    int dst_on_device, void *hip_stream) {

@@ -74,6 +74,43 @@ __device__ __forceinline__ int pm_digit(const uint8_t *k, int w, int nbits) {
   return (int)(v & 1u) + (int)((v >> 1) & 7u) - 8 * (int)(v >> 4);
 }
 
+// The window loop of a ladder (the head of points_mult.hip), shared by k_pm_ladder
+// and the NTT over points (points_ntt.hip): acc = [k] P for the lane (pair) whose
+// rows are mine[(m - 1) np], m = 1 .. 8, and whose scalar is k.  Every lane of a
+// wave runs the same windows and doublings; a zero digit or an all-zero row is
+// skipped under a predicate taken by whole pairs.
+template <int G>
+__device__ __forceinline__ void pm_ladder_loop(Xyzz<typename PmLane<G>::LF> &acc,
+                                               const Aff<typename FieldOf<G>::F> *__restrict__ mine, size_t np,
+                                               const uint8_t *__restrict__ k, int nbits, int comp) {
+  typedef typename PmLane<G>::LF LF;
+  const int nw = nbits / 4 + 1;
+  xyzz_set_inf(acc);
+#pragma unroll 1
+  for (int w = nw - 1; w >= 0; --w) {
+    const int d = pm_digit(k, w, nbits);
+    const uint32_t m = (uint32_t)(d < 0 ? -d : d);
+    // the row is asked for before the doublings, which hide its latency
+    Aff<LF> row;
+    f_zero(row.x);
+    f_zero(row.y);
+    if (m) {
+      const Aff<typename FieldOf<G>::F> *r = mine + (size_t)(m - 1) * np;
+      pm_ld(row.x, &r->x, comp);
+      pm_ld(row.y, &r->y, comp);
+    }
+    if (w != nw - 1) {
+#pragma unroll 1
+      for (int j = 0; j < 4; ++j) {
+        Xyzz<LF> tmp = acc;
+        xyzz_dbl(acc, tmp);
+      }
+    }
+    const bool zx = f_is_zero_exact(row.x), zy = f_is_zero_exact(row.y);
+    if (!(zx & zy)) xyzz_madd(acc, row, d < 0);  // (a zero digit left the row zero)
+  }
+}
+
 // lane (pair) t < n: rows[t] = P_t (canonical internal limbs; infinity all zero),
 // xz[(m - 2) n + t] = [m] P_t for m = 2 .. 8
 template <int G>

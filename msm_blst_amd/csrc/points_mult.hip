@@ -65,32 +65,8 @@ static __global__ void __launch_bounds__(128, 2)
   if (t >= n) return;  // whole pairs only
   const uint8_t *k = sc + t * stride;
   const Aff<typename FieldOf<G>::F> *mine = rows + (np == 1 ? 0 : t);
-  const int nw = nbits / 4 + 1;
   Xyzz<LF> acc;
-  xyzz_set_inf(acc);
-#pragma unroll 1
-  for (int w = nw - 1; w >= 0; --w) {
-    const int d = pm_digit(k, w, nbits);
-    const uint32_t m = (uint32_t)(d < 0 ? -d : d);
-    // the row is asked for before the doublings, which hide its latency
-    Aff<LF> row;
-    f_zero(row.x);
-    f_zero(row.y);
-    if (m) {
-      const Aff<typename FieldOf<G>::F> *r = mine + (size_t)(m - 1) * np;
-      pm_ld(row.x, &r->x, comp);
-      pm_ld(row.y, &r->y, comp);
-    }
-    if (w != nw - 1) {
-#pragma unroll 1
-      for (int j = 0; j < 4; ++j) {
-        Xyzz<LF> tmp = acc;
-        xyzz_dbl(acc, tmp);
-      }
-    }
-    const bool zx = f_is_zero_exact(row.x), zy = f_is_zero_exact(row.y);
-    if (!(zx & zy)) xyzz_madd(acc, row, d < 0);  // (a zero digit left the row zero)
-  }
+  pm_ladder_loop<G>(acc, mine, np, k, nbits, comp);  // (pm_common.hpp)
   pm_st_xyzz(&out[t], acc, comp);
 }
 
